@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: APSP node-pairs/s (routing build) + packets relayed/s per round (relay).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the result
+line.  ``--dump-outputs DIR`` also writes what the last timed step computed, the table a caller
+of the build receives, as DIR/lat.npy (float64, ns: exact, every latency is below 2^53) and
+DIR/loss.npy (float32); the graph is seeded, so two builds of the project can be compared entry
+for entry.  ``--full`` adds every side leg, check and CPU baseline listed below.
 
 Headline (``value``): one step is one routing build of BASELINE config 2 (1000-node complete GML
 graph, 1000 used nodes) from the device-resident arc CSR to the full 1000 x 1000 (latency u64,
@@ -11,7 +17,7 @@ loss f32) table resident in HBM.  At N > 1 the source rows are sharded over the 
 collective inside the SSSP) and the table is all-gathered over RCCL so every rank ends with the
 full table; the timed region includes that all-gather (strong scaling: the graph is fixed).
 
-Side legs, each its own JSON object in the same line:
+Side legs (``--full`` only), each its own JSON object in the same line:
   * ``relay`` -- C5: one round of 100k hosts / 10M packets per step (stamp + loss draw + bucket
     by destination + per-destination sort), inputs resident in HBM.  At N > 1 the hosts are
     sharded by id, every rank stamps its own sources, and the engine exchanges the events over
@@ -23,7 +29,7 @@ Side legs, each its own JSON object in the same line:
   * ``routing_e2e`` / ``relay.e2e_host_buffers`` -- SURVEY 8(d)'s end-to-end figures (host
     buffers in and out, PCIe included); ``relay.equeue`` -- relay + device event-queue merge.
 Rank 0 prints ONE JSON line.  Timing: barrier + device sync on both sides of exactly K steps,
-max over ranks.  The CPU baselines (rank 0, N = 1) time the C restatement of the reference
+max over ranks.  The CPU baselines (``--full``, rank 0, N = 1) time the C restatement of the reference
 (oracle/c) on bounded samples of the same workloads.
 """
 from __future__ import annotations
@@ -1148,6 +1154,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's table as DIR/lat.npy (float64) and DIR/loss.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs, the checks and the CPU baselines (the options below shape them)")
     ap.add_argument("--relay-steps", type=int, default=None)
     ap.add_argument("--c4-steps", type=int, default=1)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1161,6 +1171,8 @@ def main():
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--c4-no-gather", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     world, rank, local = dist_setup(args.gpus)
     from shadow_amd.routing import Engine
     eng = Engine(local)
@@ -1171,9 +1183,10 @@ def main():
             host_comm = D.HostComm(eng)   # (kept alive: it holds the transport callback)
         else:
             D.comm_init_rccl(eng)
-    cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
 
     r = routing_leg(eng, world, rank, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
     value = args.steps * r["n"] ** 2 / r["dt"]
     res = {
         "metric": METRIC, "value": value, "unit": "node-pairs/s", "n_gpus": world,
@@ -1195,6 +1208,27 @@ def main():
                      "work": "2 int ops (add, min) per arc relaxation per source row = 2*n*A "
                              "(A = arcs before pruning: the reference's Dijkstra work)"},
     }
+    if args.full:
+        full_legs(args, eng, world, rank, r, res)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    eng.close()
+    del host_comm
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, r):
+    """--dump-outputs: the table the last timed step left, as a caller of the build receives it."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "lat.npy"), r["lat"].astype(np.float64))
+    np.save(os.path.join(path, "loss.npy"), r["loss"].astype(np.float32))
+
+
+def full_legs(args, eng, world, rank, r, res):
+    """--full: the CPU baselines, the checks and every side leg, added to the result line."""
+    cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
     if cpu:
         cb, fa, ti = cpu_baseline_routing(r["el"])
         cpu_bit_exact(cb, fa, ti, r["lat"], r["loss"])
@@ -1268,13 +1302,6 @@ def main():
         res["codel"] = codel_leg(eng, cpu=cpu)
     if world == 1 and not args.no_tbucket:
         res["tbucket"] = tbucket_leg(eng, cpu=cpu)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    eng.close()
-    del host_comm
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

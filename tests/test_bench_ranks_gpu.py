@@ -18,7 +18,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, SHD_BENCH_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "4",
-           "--warmup", "1", "--relay-steps", "2", "--no-c3", "--no-c4", "--no-codel", "--no-tbucket"]
+           "--warmup", "1", "--full", "--relay-steps", "2", "--no-c3", "--no-c4", "--no-codel", "--no-tbucket"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

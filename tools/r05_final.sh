@@ -5,10 +5,11 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+out=${OUT_DIR:-bench_out}; mkdir -p "$out"   # the bench's own line and log
 if [ "$1" = 1 ]; then
-  timeout -k 10 400 python3 -u bench.py > gpurun_out/r05_bench.json 2> gpurun_out/r05_bench.err &&
+  timeout -k 10 400 python3 -u bench.py --full > "$out/r05_bench.json" 2> "$out/r05_bench.err" &&
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r05_prof_bench -o run -- \
-    python3 bench.py --no-cpu-baseline > gpurun_out/r05_prof_bench.log 2>&1 &&
+    python3 bench.py --full --no-cpu-baseline > "$out/r05_prof_bench.log" 2>&1 &&
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r05_prof_relay -o run -- \
     python3 tools/relay_only.py 10 > gpurun_out/r05_prof_relay.log 2>&1 &&
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r05_prof_equeue -o run -- \

@@ -19,7 +19,7 @@ for v in "$@"; do
 done
 for rep in $( [ -z "$NO_AB" ] && echo 1 2 ); do
   for v in "$@"; do
-    env $(echo "$v" | tr ',' ' ') timeout -k 10 150 python3 bench.py --steps 5 --no-cpu-baseline --no-c3 --no-c4 \
+    env $(echo "$v" | tr ',' ' ') timeout -k 10 150 python3 bench.py --full --steps 5 --no-cpu-baseline --no-c3 --no-c4 \
       --no-c5b --no-codel --no-tbucket --no-e2e 2> gpurun_out/r06_ab.err > gpurun_out/r06_ab.json || { tail -20 gpurun_out/r06_ab.err; exit 3; }
     python3 - "$v" <<'PY'
 import json, sys

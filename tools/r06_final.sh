@@ -12,9 +12,10 @@ if [ "$1" = tests ]; then
   timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread \
     > gpurun_out/r06_gputests.log 2>&1; rc=$?; tail -5 gpurun_out/r06_gputests.log; exit $rc
 elif [ "$1" = 1 ]; then
-  timeout -k 10 500 python3 -u bench.py > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err &&
+  out=${OUT_DIR:-bench_out}; mkdir -p "$out"   # the bench's own line and log
+  timeout -k 10 500 python3 -u bench.py --full > "$out/r06_bench.json" 2> "$out/r06_bench.err" &&
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r06_prof_bench -o run -- \
-    python3 bench.py --no-cpu-baseline > gpurun_out/r06_prof_bench.log 2>&1 &&
+    python3 bench.py --full --no-cpu-baseline > "$out/r06_prof_bench.log" 2>&1 &&
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r06_prof_relay -o run -- \
     python3 tools/relay_only.py 10 > gpurun_out/r06_prof_relay.log 2>&1 &&
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r06_prof_equeue -o run -- \

@@ -22,7 +22,7 @@ done
 for rep in $( [ -z "$NO_AB" ] && echo 1 2 ); do
   for lib in "$@"; do
     export SHD_ACCEL_LIB=$PWD/ablibs/$lib.so
-    timeout -k 10 150 python3 bench.py --steps 5 --no-cpu-baseline --no-c3 --no-c4 --no-codel --no-tbucket \
+    timeout -k 10 150 python3 bench.py --full --steps 5 --no-cpu-baseline --no-c3 --no-c4 --no-codel --no-tbucket \
       --no-e2e 2>/dev/null > gpurun_out/r06_ab.json || exit 3
     python3 - "$lib" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 var=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
-    env "$var=$v" timeout -k 10 150 python3 bench.py --steps 10 --no-cpu-baseline --no-c3 --no-c4 --no-codel \
+    env "$var=$v" timeout -k 10 150 python3 bench.py --full --steps 10 --no-cpu-baseline --no-c3 --no-c4 --no-codel \
       --no-tbucket --no-e2e --no-equeue 2>/dev/null > gpurun_out/reab.json || exit 3
     python3 - "$var=$v" <<'PY'
 import json, sys

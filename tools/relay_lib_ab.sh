@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 for rep in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = default ]; then unset SHD_ACCEL_LIB; else export SHD_ACCEL_LIB=$lib; fi
-    timeout -k 10 150 python3 bench.py --steps 5 --no-cpu-baseline --no-c3 --no-c4 --no-codel --no-tbucket \
+    timeout -k 10 150 python3 bench.py --full --steps 5 --no-cpu-baseline --no-c3 --no-c4 --no-codel --no-tbucket \
       --no-e2e 2>/dev/null > gpurun_out/rlab.json || exit 3
     python3 - "$(basename $lib)" <<'PY'
 import json, sys
