@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 3
+#define SHD_ABI_VERSION 4
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -595,6 +595,72 @@ shd_status shd_tb_setup(shd_ctx* ctx, uint32_t n_relays, const uint64_t* capacit
  * the batch still ran. */
 shd_status shd_tb_run_device(shd_ctx* ctx, const shd_tb_ops* ops, uint8_t* status, uint64_t* value);
 shd_status shd_tb_get_state(shd_ctx* ctx, uint32_t relay, shd_tb_state* out);
+
+/* ---------------------------------------------------------------------------------------
+ * Inbound stage: the destination side after the event queues, for every host at once.  Per host
+ * the device keeps a CoDel router queue, the inbound relay's token bucket and the relay's state
+ * (the time of its outstanding forward task, the one packet it has cached) -- the stage's own
+ * state: shd_codel_* and shd_tb_* keep their queues and buckets and behave as before.  One call
+ * consumes a window's popped packet events, per host in order and merged with the host's own
+ * forward task (a packet event runs before a task of the same time, event.rs:102-110):
+ *   packet event at t   CoDelQueue::push(pkt, t) (Host::execute's packet branch, host.rs:742-746,
+ *                       Router::route_incoming_packet), then Relay::notify (relay/mod.rs:110-135):
+ *                       an Idle relay gets a task at t, a Pending one nothing
+ *   task at T < window_end   Relay::forward_until_blocked (relay/mod.rs:200-272) at T: take the
+ *                       cached packet or CoDelQueue::pop(T) (which may drop packets first, and
+ *                       may return none: Idle); unless T < bootstrap_end or the host has no
+ *                       bucket, conforming_remove(size) at T; Err(d) caches the packet and
+ *                       schedules the next task at T + d (EmulatedTime saturating); otherwise
+ *                       the packet is forwarded at T and the loop goes on
+ * A task at T >= window_end stays outstanding for a later call.  Inbound packets are never local
+ * (the router's address is UNSPECIFIED, host.rs:281-292).  Not covered: the reference's CPU-delay
+ * model (host.rs:708-735) reschedules events on the CPU side; a caller that enables it cannot use
+ * this stage.
+ * ------------------------------------------------------------------------------------- */
+#define SHD_INBOUND_FORWARDED 1   /* (pkt, T): the packet reaches the interface at T */
+#define SHD_INBOUND_DROPPED 2     /* (pkt, T): dropped by the pop at T */
+
+/* (Re)create n_hosts empty queues of up to `capacity` packets each, Idle relays and full
+ * buckets.  The tb_* host arrays follow shd_tb_setup's rules (all three parameters 0: no bucket). */
+shd_status shd_inbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t capacity,
+                             const uint64_t* tb_capacity, const uint64_t* tb_refill_increment,
+                             const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill);
+/*
+ * Advance every host over the window ending at window_end.  Device inputs: host h's events are
+ * [d_off[h], d_off[h+1]) of d_time / d_size (total packet size) / d_pkt (packet id, not
+ * UINT32_MAX); d_off and d_time may be shd_equeue_out.off and .deliver as they lie on the device
+ * (n_events = n_popped; every pointer may be NULL when n_events is 0).  Input contract, per host:
+ * times non-decreasing, every time < window_end and >= the previous call's window_end; for a host
+ * with a bucket every size <= the bucket's capacity (the reference never sees a larger packet --
+ * total size <= CONFIG_MTU -- and would reschedule it forever).  Outputs: one record per packet
+ * that left the stage in this window, grouped by host in the order they happened (the drops of
+ * a pop before the packet it returned), in engine-owned device arrays valid until the next
+ * advance: host h's records are [out_off[h], out_off[h+1]) of out_pkt / out_time / out_kind
+ * (SHD_INBOUND_*), *n_out in all.  *n_stored = packets still queued or cached; *next_task_time =
+ * the earliest outstanding forward task over the hosts (UINT64_MAX: none).  The forward task is a
+ * local event of its host: fold *next_task_time into shd_round_window's cpu_next_event_time.
+ * Any output pointer may be NULL.  No collective: on a sharded context the arrays cover the
+ * rank's own hosts, as the event queues' arrays do.
+ * SHD_ERR_INVALID: the input contract is violated, d_off is not a CSR over n_events events, or a
+ * queue exceeded its capacity -- every such input is refused by a check in the kernel, the
+ * window has partly run, and every later call returns SHD_ERR_STATE until shd_inbound_setup; also
+ * where the reference panics (a time before a bucket's last refill).  A NULL array with
+ * n_events > 0 or a window_end below the previous one is SHD_ERR_INVALID before anything runs.
+ */
+shd_status shd_inbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                               const uint32_t* d_size, const uint32_t* d_pkt, uint64_t n_events,
+                               uint64_t window_end, uint64_t bootstrap_end,
+                               const uint32_t** out_off, const uint32_t** out_pkt,
+                               const uint64_t** out_time, const uint8_t** out_kind,
+                               uint64_t* n_out, uint64_t* n_stored, uint64_t* next_task_time);
+/* One host's state (any pointer may be NULL): *task_time UINT64_MAX = Idle; the cached packet;
+ * the queue and the bucket in the structs of shd_codel_get_state / shd_tb_get_state
+ * (pending_until = the task time, 0 when Idle).  SHD_ERR_STATE while the stage is not ready --
+ * before shd_inbound_setup, or after a contract error until the next setup, as the advance;
+ * SHD_ERR_INVALID: host >= n_hosts. */
+shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_time, uint32_t* has_cached,
+                                 uint32_t* cached_pkt, uint32_t* cached_size, shd_codel_state* codel,
+                                 shd_tb_state* bucket);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

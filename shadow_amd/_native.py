@@ -39,6 +39,7 @@ EXPORTED = [
     "shd_routing_lookup_batch", "shd_routing_mirror", "shd_equeue_batch_buffers",
     "shd_set_knob", "shd_get_knob", "shd_relay_flush", "shd_host_alloc", "shd_host_free",
     "shd_comm_init_host",
+    "shd_inbound_setup", "shd_inbound_advance", "shd_inbound_get_state",
 ]
 COMM_ID_BYTES = 128
 
@@ -223,6 +224,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_host_free": (None, [P]),
         "shd_get_knob": (I32, [P, C.c_char_p, P]),
         "shd_comm_init_host": (I32, [P, I32, I32, P]),
+        "shd_inbound_setup": (I32, [P, U32, U32, P, P, P, P]),
+        "shd_inbound_advance": (I32, [P, P, P, P, P, U64, U64, U64, P, P, P, P, P, P, P]),
+        "shd_inbound_get_state": (I32, [P, U32, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

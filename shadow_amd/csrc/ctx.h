@@ -130,6 +130,23 @@ struct TbState {   // token-bucket relays (tbucket.hip)
     bool ready = false;
 };
 
+// The inbound stage (inbound.hip): per host a CoDel queue, the inbound relay's token bucket and
+// the relay words -- its own state, apart from CodelState / TbState above.
+struct InboundState {
+    DevBuf st, flags, ring;        // the queues: CodelHost, flag word, ring of `cap` packets per host
+    DevBuf tb;                     // TbRelay per host
+    DevBuf rl;                     // InRelay per host: outstanding task time, the cached packet
+    DevBuf cnt, nrec;              // [n_hosts + 1] record region bounds -> offsets; records written
+    DevBuf r_pkt, r_time, r_kind;  // the records in their per-host regions
+    DevBuf o_off, o_pkt, o_time, o_kind;   // the compact output of the last advance
+    DevBuf words;                  // status, n_out, n_stored, min task time
+    ScanScratch scan;
+    uint32_t n_hosts = 0, cap = 0;
+    uint64_t n_stored = 0;         // packets queued or cached after the last advance
+    uint64_t prev_end = 0;         // the last advance's window_end
+    bool ready = false;
+};
+
 struct RelayState {
     bool ready = false;
     uint32_t n_hosts = 0;
@@ -225,7 +242,7 @@ struct PreparedGraph {
 struct shd_ctx;
 namespace shd {
 // h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [32, 34) flush checks,
-// [48, 48 + 4 + runs + 1) event-queue counts; [80] is the polled marker
+// [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker
 constexpr int kPinWords = 88;
 constexpr int kPinMarker = 80;
 // Wait until everything enqueued on stream s has finished (see api.cpp)
@@ -291,4 +308,5 @@ struct shd_ctx {
     shd::RoundState rnd;
     shd::CodelState codel;
     shd::TbState tb;
+    shd::InboundState inb;
 };

@@ -23,37 +23,12 @@
 #include <vector>
 
 #include "ctx.h"
+#include "tbucket_ops.h"
 
 namespace shd {
 
-constexpr uint64_t kSimtimeMax = 17500059273709551614ull;   // simulation_time.rs:377
-constexpr uint64_t kEmutimeMax = ~0ull - 1ull;               // emulated_time.rs:27
 constexpr uint8_t kTbForwarded = 0, kTbBlocked = 1, kTbSkipped = 2;
 constexpr uint8_t kTbExempt = 1;
-
-struct TbRelay {   // 48 bytes per relay; capacity 0 = no bucket (unlimited)
-    uint64_t capacity, balance, increment, interval, last_refill, pending;
-};
-
-// SimulationTime::saturating_mul / saturating_add (simulation_time.rs:135-148)
-__device__ __forceinline__ uint64_t simtime_sat_mul(uint64_t t, uint64_t k, bool& bad) {
-    const uint64_t hi = __umul64hi(t, k);
-    if (hi) return kSimtimeMax;
-    const uint64_t p = t * k;
-    bad |= p > kSimtimeMax;
-    return p;
-}
-__device__ __forceinline__ uint64_t simtime_sat_add(uint64_t a, uint64_t b, bool& bad) {
-    const uint64_t s = a + b;
-    if (s < a) return kSimtimeMax;
-    bad |= s > kSimtimeMax;
-    return s;
-}
-// EmulatedTime::saturating_add (emulated_time.rs:95-108)
-__device__ __forceinline__ uint64_t emutime_sat_add(uint64_t t, uint64_t d) {
-    const uint64_t s = t + d;
-    return (s < t || s > kEmutimeMax) ? kEmutimeMax : s;
-}
 
 constexpr uint32_t kAttBatch = 8;   // attempts per lane loaded ahead of the state machine
 
@@ -95,30 +70,7 @@ __global__ __launch_bounds__(256) void tb_run(uint32_t n_relays, const uint32_t*
             } else if (fl[i] & kTbExempt) { // local or bootstrapping: no tokens taken
                 v = s.balance;
             } else {
-                // lazy_refill (token_bucket.rs:127-157)
-                const bool before = now < s.last_refill;   // duration_since(..).unwrap() panics
-                bad |= before;
-                uint64_t span = before ? 0ull : now - s.last_refill;
-                if (span >= s.interval) {
-                    const uint64_t n = span / s.interval;
-                    const uint64_t tok = __umul64hi(s.increment, n) ? ~0ull : s.increment * n;
-                    const uint64_t sum = s.balance + tok < s.balance ? ~0ull : s.balance + tok;
-                    s.balance = sum < s.capacity ? sum : s.capacity;
-                    s.last_refill = emutime_sat_add(s.last_refill, simtime_sat_mul(s.interval, n, bad));
-                    bad |= now < s.last_refill;
-                    span = now < s.last_refill ? 0ull : now - s.last_refill;
-                }
-                const uint64_t next_span = s.interval - span;
-                const uint64_t dec = sz[i];
-                if (s.balance >= dec) {
-                    s.balance -= dec;
-                    v = s.balance;
-                } else {   // compute_conforming_duration (token_bucket.rs:94-120)
-                    const uint64_t req = dec - s.balance;
-                    const uint64_t nr = req / s.increment + (req % s.increment ? 1u : 0u);
-                    v = nr == 0 ? 0ull
-                      : nr == 1 ? next_span
-                                : simtime_sat_add(next_span, simtime_sat_mul(s.interval, nr - 1, bad), bad);
+                if (!tb_conforming_remove(s, now, sz[i], v, bad)) {
                     stt = kTbBlocked;
                     s.pending = emutime_sat_add(now, v);
                 }
@@ -140,15 +92,9 @@ extern "C" {
 shd_status shd_tb_setup(shd_ctx* ctx, uint32_t n_relays, const uint64_t* capacity,
                         const uint64_t* refill_increment, const uint64_t* refill_interval_ns,
                         const uint64_t* last_refill) {
-    if (!ctx || (n_relays && (!capacity || !refill_increment || !refill_interval_ns || !last_refill)))
-        return SHD_ERR_INVALID;
-    std::vector<TbRelay> h(n_relays);
-    for (uint32_t r = 0; r < n_relays; ++r) {
-        const bool any = capacity[r] || refill_increment[r] || refill_interval_ns[r];
-        const bool all = capacity[r] && refill_increment[r] && refill_interval_ns[r];
-        if (any && !all) return SHD_ERR_INVALID;   // TokenBucket::new -> None (the reference unwraps)
-        h[r] = TbRelay{capacity[r], capacity[r], refill_increment[r], refill_interval_ns[r], last_refill[r], 0};
-    }
+    if (!ctx) return SHD_ERR_INVALID;
+    std::vector<TbRelay> h;
+    SHD_TRY(tb_rows(n_relays, capacity, refill_increment, refill_interval_ns, last_refill, h));
     TbState& T = ctx->tb;
     SHD_HIP(hipSetDevice(ctx->device));
     SHD_TRY(T.st.ensure(std::max<size_t>(n_relays, 1) * sizeof(TbRelay)));

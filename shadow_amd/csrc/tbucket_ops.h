@@ -1,0 +1,99 @@
+// One relay's token bucket: the arithmetic tbucket.hip (attempt replay) and inbound.hip (the
+// inbound stage) both compile.
+//
+// Reference semantics: src/main/network/relay/token_bucket.rs (FlyearthR/shadow)
+//   :37-60   new_inner: a bucket only when capacity, increment and interval are all non-zero;
+//            it starts full
+//   :75-86   conforming_remove: lazy refill, then balance.checked_sub(decrement) or the
+//            conforming duration
+//   :94-120  compute_conforming_duration: ceil(missing / increment) refills; 0 -> ZERO,
+//            1 -> the span to the next refill, n -> span + interval * (n - 1), saturating
+//   :127-157 lazy_refill: n = elapsed / interval whole refills, balance + increment * n
+//            (u64 saturating) clamped to the capacity, last_refill += interval * n
+// Times: EmulatedTime ns (u64); SimulationTime saturates at SIMTIME_MAX, EmulatedTime at
+// EMUTIME_MAX.  A product or sum beyond SIMTIME_MAX that does not overflow u64 is where the
+// reference panics (from_c_simtime(..).unwrap()); `bad` records it.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "common.h"
+
+namespace shd {
+
+constexpr uint64_t kSimtimeMax = 17500059273709551614ull;   // simulation_time.rs:377
+constexpr uint64_t kEmutimeMax = ~0ull - 1ull;               // emulated_time.rs:27
+
+struct TbRelay {   // 48 bytes per relay; capacity 0 = no bucket (unlimited)
+    uint64_t capacity, balance, increment, interval, last_refill, pending;
+};
+
+// SimulationTime::saturating_mul / saturating_add (simulation_time.rs:135-148)
+__device__ __forceinline__ uint64_t simtime_sat_mul(uint64_t t, uint64_t k, bool& bad) {
+    const uint64_t hi = __umul64hi(t, k);
+    if (hi) return kSimtimeMax;
+    const uint64_t p = t * k;
+    bad |= p > kSimtimeMax;
+    return p;
+}
+__device__ __forceinline__ uint64_t simtime_sat_add(uint64_t a, uint64_t b, bool& bad) {
+    const uint64_t s = a + b;
+    if (s < a) return kSimtimeMax;
+    bad |= s > kSimtimeMax;
+    return s;
+}
+// EmulatedTime::saturating_add (emulated_time.rs:95-108)
+__device__ __forceinline__ uint64_t emutime_sat_add(uint64_t t, uint64_t d) {
+    const uint64_t s = t + d;
+    return (s < t || s > kEmutimeMax) ? kEmutimeMax : s;
+}
+
+// conforming_remove(dec) at `now` (token_bucket.rs:75-86) on a relay that has a bucket: true and
+// v = the balance after the removal, or false and v = the duration until it would conform
+__device__ __forceinline__ bool tb_conforming_remove(TbRelay& s, uint64_t now, uint64_t dec, uint64_t& v,
+                                                     bool& bad) {
+    // lazy_refill (token_bucket.rs:127-157)
+    const bool before = now < s.last_refill;   // duration_since(..).unwrap() panics
+    bad |= before;
+    uint64_t span = before ? 0ull : now - s.last_refill;
+    if (span >= s.interval) {
+        const uint64_t n = span / s.interval;
+        const uint64_t tok = __umul64hi(s.increment, n) ? ~0ull : s.increment * n;
+        const uint64_t sum = s.balance + tok < s.balance ? ~0ull : s.balance + tok;
+        s.balance = sum < s.capacity ? sum : s.capacity;
+        s.last_refill = emutime_sat_add(s.last_refill, simtime_sat_mul(s.interval, n, bad));
+        bad |= now < s.last_refill;
+        span = now < s.last_refill ? 0ull : now - s.last_refill;
+    }
+    const uint64_t next_span = s.interval - span;
+    if (s.balance >= dec) {
+        s.balance -= dec;
+        v = s.balance;
+        return true;
+    }
+    // compute_conforming_duration (token_bucket.rs:94-120)
+    const uint64_t req = dec - s.balance;
+    const uint64_t nr = req / s.increment + (req % s.increment ? 1u : 0u);
+    v = nr == 0 ? 0ull
+      : nr == 1 ? next_span
+                : simtime_sat_add(next_span, simtime_sat_mul(s.interval, nr - 1, bad), bad);
+    return false;
+}
+
+// Host rows of a setup call: all three parameters 0 = no bucket; some but not all 0 is
+// SHD_ERR_INVALID (TokenBucket::new -> None, which the reference unwraps).  Buckets start full.
+inline shd_status tb_rows(uint32_t n, const uint64_t* capacity, const uint64_t* refill_increment,
+                          const uint64_t* refill_interval_ns, const uint64_t* last_refill,
+                          std::vector<TbRelay>& h) {
+    if (n && (!capacity || !refill_increment || !refill_interval_ns || !last_refill)) return SHD_ERR_INVALID;
+    h.resize(n);
+    for (uint32_t r = 0; r < n; ++r) {
+        const bool any = capacity[r] || refill_increment[r] || refill_interval_ns[r];
+        const bool all = capacity[r] && refill_increment[r] && refill_interval_ns[r];
+        if (any && !all) return SHD_ERR_INVALID;
+        h[r] = TbRelay{capacity[r], capacity[r], refill_increment[r], refill_interval_ns[r], last_refill[r], 0};
+    }
+    return SHD_OK;
+}
+
+}  // namespace shd
