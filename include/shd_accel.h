@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 4
+#define SHD_ABI_VERSION 5
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -661,6 +661,91 @@ shd_status shd_inbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64
 shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_time, uint32_t* has_cached,
                                  uint32_t* cached_pkt, uint32_t* cached_size, shd_codel_state* codel,
                                  shd_tb_state* bucket);
+
+/* ---------------------------------------------------------------------------------------
+ * Outbound stage: the source side up to Worker::send_packet, for every host at once -- the
+ * outbound relay relay_inet_out (host.rs:285-288, :871-880).  Per host the device keeps the
+ * network interface's queue (the packets its sockets have offered and that have not left yet,
+ * ordered by packet priority: the FIFO queuing discipline, network_interface.c:276-316,
+ * network_queuing_disciplines.c:90-102, pops the socket whose head packet has the lowest
+ * priority; priorities come from one per-host counter, host.rs:604-610, and every socket offers
+ * its packets in increasing priority, so that is the lowest priority over all queued packets),
+ * the outbound relay's token bucket, the relay's state (the time of its outstanding forward
+ * task, the one packet it has cached) and the host's global id first_host + h -- the stage's own
+ * state, apart from shd_inbound_* and shd_tb_*.  One call consumes a window's offers ("socket
+ * data became sendable": notify_socket_has_packets, then Relay::notify), per host in order and
+ * merged with the host's own forward task:
+ *   offer at t <= task  (or the relay is Idle)  the packet is inserted by priority; an Idle relay
+ *                       gets a task at t (notify -> forward_later(ZERO), relay/mod.rs:110-135),
+ *                       a Pending one nothing.  An offer at the task's own time is inserted
+ *                       before the task runs: the sends of one event accumulate (:124-126)
+ *   task at T < window_end   Relay::forward_until_blocked (relay/mod.rs:200-272) at T: take the
+ *                       cached packet or the lowest-priority queued one (none: Idle).  A packet
+ *                       with dst == first_host + h is local (:222-230): it is forwarded at T
+ *                       without the bucket and goes back to the interface (:262-265), a LOCAL
+ *                       record, not sent.  Otherwise, unless T < bootstrap_end or the host has no
+ *                       bucket, conforming_remove(size) at T; Err(d) caches the packet and
+ *                       schedules the next task at T + d (EmulatedTime saturating); on success
+ *                       the packet is sent at T, the instant Router::push calls
+ *                       Worker::send_packet (router/mod.rs:49-55), and the loop goes on
+ * A task at T >= window_end stays outstanding for a later call.  The cached packet is never
+ * overtaken, not by a local packet and not by a lower priority (head-of-line blocking).
+ * Exactness: the merge is exact whenever a host's offers at one instant arrive in increasing
+ * priority -- everything but a same-instant retransmission -- and also when the bucket does not
+ * block at that instant.  Not covered: the round-robin discipline (network_interface.c:235-273;
+ * FIFO is the default, configuration.rs:495), the loopback relay (unlimited, every packet local),
+ * the pcap and tracker side effects of networkinterface_pop, and the CPU-delay model
+ * (host.rs:708-735), as the inbound stage.
+ * ------------------------------------------------------------------------------------- */
+
+/* (Re)create n_hosts empty queues of up to `capacity` packets each, Idle relays and full
+ * buckets; host h's global id (what a packet's dst is compared with) is first_host + h.  The tb_*
+ * host arrays follow shd_tb_setup's rules (all three parameters 0: no bucket). */
+shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
+                              const uint64_t* tb_capacity, const uint64_t* tb_refill_increment,
+                              const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill);
+/*
+ * Advance every host over the window ending at window_end.  Device inputs: host h's offers are
+ * [d_off[h], d_off[h+1]) of d_time / d_prio (FifoPacketPriority) / d_size (total packet size: what
+ * the bucket removes) / d_payload (packet_getPayloadSize, passed through to shd_batch.payload) /
+ * d_dst (destination HostId) / d_pkt (the caller's packet id, not UINT32_MAX); every pointer may
+ * be NULL when n_offers is 0.  Input contract, per host: times non-decreasing, every time
+ * < window_end and >= the previous call's window_end; priorities unique among the packets queued
+ * on the host; for a host with a bucket every non-local size <= the bucket's capacity.
+ * Outputs, engine-owned device arrays valid until the next advance:
+ *   *d_batch_out   src_off[n_hosts+1], send_time / dst_host / payload of the packets sent, grouped
+ *                  by host in send order, n_packets, chance = NULL: it can be passed to
+ *                  shd_relay_round_device or shd_relay_round_sharded as it stands (with first_host
+ *                  = the rank's shard start it is the sharded call's layout)
+ *   *sent_pkt      sent_pkt[i] = the packet id of batch entry i
+ *   *loc_off, *loc_pkt, *loc_time   the local deliveries as a second CSR, *n_local in all: host
+ *                  h's are [loc_off[h], loc_off[h+1]) in the order they happened
+ * *n_stored = packets still queued or cached; *next_task_time = the earliest outstanding forward
+ * task over the hosts (UINT64_MAX: none): fold it into shd_round_window's cpu_next_event_time, as
+ * the inbound stage's.  Any output pointer may be NULL.  No collective.
+ * SHD_ERR_INVALID: the input contract is violated (an offer's time is checked before it is
+ * weighed against the task), d_off is not a CSR over n_offers offers, a priority equals one still
+ * queued on that host, or a queue exceeded its capacity -- every such input is refused by a check
+ * in the kernel, the window has partly run, and every later call returns SHD_ERR_STATE until
+ * shd_outbound_setup; also where the reference panics (a time before a bucket's last refill).  A
+ * NULL array with n_offers > 0 or a window_end below the previous one is SHD_ERR_INVALID before
+ * anything runs.
+ */
+shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
+                                const uint32_t* d_dst, const uint32_t* d_pkt, uint64_t n_offers,
+                                uint64_t window_end, uint64_t bootstrap_end,
+                                shd_batch* d_batch_out, const uint32_t** sent_pkt,
+                                const uint32_t** loc_off, const uint32_t** loc_pkt, const uint64_t** loc_time,
+                                uint64_t* n_local, uint64_t* n_stored, uint64_t* next_task_time);
+/* One host's state (any pointer may be NULL): *task_time UINT64_MAX = Idle; the cached packet;
+ * the queue's length and the packet at its head (the lowest priority; UINT32_MAX: empty); the
+ * bucket in the struct of shd_tb_get_state (pending_until = the task time, 0 when Idle).
+ * SHD_ERR_STATE while the stage is not ready -- before shd_outbound_setup, or after a contract
+ * error until the next setup, as the advance; SHD_ERR_INVALID: host >= n_hosts. */
+shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_time, uint32_t* has_cached,
+                                  uint32_t* cached_pkt, uint32_t* cached_size, uint32_t* queue_len,
+                                  uint32_t* head_pkt, shd_tb_state* bucket);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

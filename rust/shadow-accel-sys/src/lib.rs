@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 4;
+pub const SHD_ABI_VERSION: u32 = 5;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -229,6 +229,9 @@ extern "C" {
     pub fn shd_inbound_setup(ctx: *mut shd_ctx, n_hosts: u32, capacity: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
     pub fn shd_inbound_advance(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_size: *const u32, d_pkt: *const u32, n_events: u64, window_end: u64, bootstrap_end: u64, out_off: *mut *const u32, out_pkt: *mut *const u32, out_time: *mut *const u64, out_kind: *mut *const u8, n_out: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
     pub fn shd_inbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, codel: *mut shd_codel_state, bucket: *mut shd_tb_state) -> shd_status;
+    pub fn shd_outbound_setup(ctx: *mut shd_ctx, n_hosts: u32, first_host: u32, capacity: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
+    pub fn shd_outbound_advance(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, bootstrap_end: u64, d_batch_out: *mut shd_batch, sent_pkt: *mut *const u32, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
+    pub fn shd_outbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, queue_len: *mut u32, head_pkt: *mut u32, bucket: *mut shd_tb_state) -> shd_status;
     pub fn shd_gml_parse(text: *const c_char, len: usize, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_load(path: *const c_char, xz: i32, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_graph(g: *const shd_gml, view: *mut shd_graph) -> shd_status;

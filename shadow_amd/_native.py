@@ -40,6 +40,7 @@ EXPORTED = [
     "shd_set_knob", "shd_get_knob", "shd_relay_flush", "shd_host_alloc", "shd_host_free",
     "shd_comm_init_host",
     "shd_inbound_setup", "shd_inbound_advance", "shd_inbound_get_state",
+    "shd_outbound_setup", "shd_outbound_advance", "shd_outbound_get_state",
 ]
 COMM_ID_BYTES = 128
 
@@ -227,6 +228,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_inbound_setup": (I32, [P, U32, U32, P, P, P, P]),
         "shd_inbound_advance": (I32, [P, P, P, P, P, U64, U64, U64, P, P, P, P, P, P, P]),
         "shd_inbound_get_state": (I32, [P, U32, P, P, P, P, P, P]),
+        "shd_outbound_setup": (I32, [P, U32, U32, U32, P, P, P, P]),
+        "shd_outbound_advance": (I32, [P, P, P, P, P, P, P, P, U64, U64, U64, P, P, P, P, P, P, P, P]),
+        "shd_outbound_get_state": (I32, [P, U32, P, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -147,6 +147,24 @@ struct InboundState {
     bool ready = false;
 };
 
+// The outbound stage (outbound.hip): per host the interface's priority queue, the outbound relay's
+// token bucket and the relay words -- its own state, apart from InboundState / TbState above.
+struct OutboundState {
+    DevBuf ring;                   // OutPkt ring of `cap` slots per host, sorted by priority: all but the first packet
+    DevBuf tb;                     // TbRelay per host
+    DevBuf rl;                     // OutRelay per host: task time, the queue's first packet, ring head / count, the cached packet
+    DevBuf cnt, nsent, nloc;       // [n_hosts + 1] record region bounds -> offsets; SENT / LOCAL records written
+    DevBuf r_pkt, r_time, r_dst, r_pay;    // the records in their per-host regions (SENT front, LOCAL back)
+    DevBuf src_off, b_time, b_dst, b_pay, b_pkt;   // the last advance's batch (shd_batch) and its packet ids
+    DevBuf loc_off, l_pkt, l_time;         // the last advance's local deliveries
+    DevBuf words;                  // status, n_sent, n_local, n_stored, min task time
+    ScanScratch scan;
+    uint32_t n_hosts = 0, first_host = 0, cap = 0;
+    uint64_t n_stored = 0;         // packets queued or cached after the last advance
+    uint64_t prev_end = 0;         // the last advance's window_end
+    bool ready = false;
+};
+
 struct RelayState {
     bool ready = false;
     uint32_t n_hosts = 0;
@@ -242,7 +260,8 @@ struct PreparedGraph {
 struct shd_ctx;
 namespace shd {
 // h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [32, 34) flush checks,
-// [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker
+// [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker;
+// [81, 86) outbound-stage words
 constexpr int kPinWords = 88;
 constexpr int kPinMarker = 80;
 // Wait until everything enqueued on stream s has finished (see api.cpp)
@@ -309,4 +328,5 @@ struct shd_ctx {
     shd::CodelState codel;
     shd::TbState tb;
     shd::InboundState inb;
+    shd::OutboundState outb;
 };

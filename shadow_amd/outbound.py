@@ -1,0 +1,152 @@
+"""Host-side mirror of the outbound stage (``shd_outbound_*``): per source host the network
+interface's FIFO queue, the outbound relay's token bucket and the relay's state, kept on the
+MI355X engine.
+
+Restates the outbound relay ``relay_inet_out`` (``src/main/host/host.rs:285-288``, ``:871-880``)
+for every host at once: the interface's FIFO queuing discipline picks the packet of the lowest
+priority (``network_interface.c:276-316``), ``Relay::forward_until_blocked``
+(``relay/mod.rs:200-272``) takes tokens from the ``bw_up`` bucket, and a packet that conforms enters
+``Worker::send_packet`` at the task's time (``router/mod.rs:49-55``).
+
+``OutboundStage(engine, capacity, refill_increment, refill_interval, last_refill, first_host=0)``
+-- bucket parameters per host, all three 0 for a host without a bucket; host ``h``'s global id is
+``first_host + h`` -- or ``OutboundStage.from_bandwidth(engine, bytes_per_second, start)``.
+``advance(off, time, prio, size, payload, dst, pkt, window_end=...)`` consumes one window's offers
+grouped by host (host arrays; ``advance_device`` takes them as they lie on the GPU) and returns the
+packets sent, as the batch a relay round takes, and the local deliveries.  No CPU fallback: without
+the native library or a gfx950 GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native as N
+from .tbucket import SIM_START, create_token_bucket
+
+IDLE = 2**64 - 1
+NO_PKT = 2**32 - 1
+
+
+@dataclass
+class DeviceBatch:
+    """What ``shd_outbound_advance`` returns: engine-owned device arrays (valid until the next
+    advance) and the call's totals.  ``batch`` goes to ``shd_relay_round_device`` as it stands;
+    ``src_off`` ... ``payload`` are its pointers, for ``Relay.round_device``."""
+    batch: N.Batch
+    sent_pkt: int          # device pointers
+    loc_off: int
+    loc_pkt: int
+    loc_time: int
+    n_sent: int
+    n_local: int
+    n_stored: int          # packets still queued or cached
+    next_task_time: int    # earliest outstanding forward task, IDLE when none
+
+
+@dataclass
+class Sent:
+    src_off: np.ndarray    # u32 [n_hosts + 1]: host h sent packets [src_off[h], src_off[h+1])
+    send_time: np.ndarray  # u64
+    dst_host: np.ndarray   # u32
+    payload: np.ndarray    # u32
+    sent_pkt: np.ndarray   # u32: the packet id of each batch entry
+    loc_off: np.ndarray    # u32 [n_hosts + 1]: host h's local deliveries
+    loc_pkt: np.ndarray    # u32
+    loc_time: np.ndarray   # u64
+    n_stored: int
+    next_task_time: int
+
+    def sent_for(self, h: int):
+        a, b = int(self.src_off[h]), int(self.src_off[h + 1])
+        return list(zip(self.sent_pkt[a:b].tolist(), self.send_time[a:b].tolist(), self.dst_host[a:b].tolist(),
+                        self.payload[a:b].tolist()))
+
+    def local_for(self, h: int):
+        a, b = int(self.loc_off[h]), int(self.loc_off[h + 1])
+        return list(zip(self.loc_pkt[a:b].tolist(), self.loc_time[a:b].tolist()))
+
+
+class OutboundStage:
+    def __init__(self, engine, capacity, refill_increment, refill_interval, last_refill=SIM_START,
+                 first_host: int = 0, ring_capacity: int = 4096):
+        self.eng = engine
+        cap = np.ascontiguousarray(capacity, np.uint64)
+        self.n_hosts = len(cap)
+        self.first_host = int(first_host)
+        inc = np.ascontiguousarray(np.broadcast_to(np.asarray(refill_increment, np.uint64), cap.shape))
+        itv = np.ascontiguousarray(np.broadcast_to(np.asarray(refill_interval, np.uint64), cap.shape))
+        last = np.ascontiguousarray(np.broadcast_to(np.asarray(last_refill, np.uint64), cap.shape))
+        N.check(engine.lib.shd_outbound_setup(engine.ctx, self.n_hosts, self.first_host, int(ring_capacity),
+                                              N.ptr(cap), N.ptr(inc), N.ptr(itv), N.ptr(last)), "shd_outbound_setup")
+
+    @classmethod
+    def from_bandwidth(cls, engine, bytes_per_second, start: int = SIM_START, first_host: int = 0,
+                       ring_capacity: int = 4096):
+        """One ``create_token_bucket`` (relay/mod.rs:291-302) of ``bw_up / 8`` bytes per second per
+        host, last refilled at ``start``; an entry of ``None`` (or a negative one) is a host without
+        a bucket."""
+        rows = [(0, 0, 0) if b is None or int(b) < 0 else create_token_bucket(int(b)) for b in bytes_per_second]
+        cap, inc, itv = (np.array([r[i] for r in rows], np.uint64) for i in range(3))
+        return cls(engine, cap, inc, itv, start, first_host, ring_capacity)
+
+    def advance_device(self, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers: int,
+                       window_end: int, bootstrap_end: int = 0) -> DeviceBatch:
+        """Device pointers (ints, ctypes pointers or torch tensors; all None for no offers)."""
+        as_p = lambda a: a if a is None or isinstance(a, (int, C.c_void_p)) else N.ptr(a)  # noqa: E731
+        b = N.Batch()
+        sp, lo, lp, lt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n_local, n_stored, nxt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        N.check(self.eng.lib.shd_outbound_advance(
+            self.eng.ctx, as_p(d_off), as_p(d_time), as_p(d_prio), as_p(d_size), as_p(d_payload), as_p(d_dst),
+            as_p(d_pkt), int(n_offers), int(window_end), int(bootstrap_end), C.byref(b), C.byref(sp), C.byref(lo),
+            C.byref(lp), C.byref(lt), C.byref(n_local), C.byref(n_stored), C.byref(nxt)), "shd_outbound_advance")
+        return DeviceBatch(b, sp.value, lo.value, lp.value, lt.value, b.n_packets, n_local.value, n_stored.value,
+                           nxt.value)
+
+    def advance(self, off=None, time=None, prio=None, size=None, payload=None, dst=None, pkt=None, *,
+                window_end: int, bootstrap_end: int = 0) -> Sent:
+        """Host arrays of one window's offers grouped by host (or none) -> host copies."""
+        keep = [None] * 7
+        n = 0
+        if off is not None:
+            import torch
+            n = len(time)
+            dev = lambda a, np_dt, dt: torch.from_numpy(np.ascontiguousarray(a, np_dt).view(dt)).cuda()  # noqa: E731
+            keep = [dev(off, np.uint32, np.int32), dev(time, np.uint64, np.int64), dev(prio, np.uint64, np.int64)] + \
+                   [dev(a, np.uint32, np.int32) for a in (size, payload, dst, pkt)]
+            assert len(keep[0]) == self.n_hosts + 1 and all(len(k) == n for k in keep[1:])
+            torch.cuda.synchronize()
+        out = self.advance_device(*keep, n, window_end, bootstrap_end)
+        del keep
+        return self.sent(out)
+
+    def sent(self, out: DeviceBatch) -> Sent:
+        """Host copies of an advance's batch and local deliveries."""
+        ns, nl = out.n_sent, out.n_local
+        src_off, loc_off = np.zeros(self.n_hosts + 1, np.uint32), np.zeros(self.n_hosts + 1, np.uint32)
+        t, d, p, sp = np.zeros(ns, np.uint64), np.zeros(ns, np.uint32), np.zeros(ns, np.uint32), np.zeros(ns, np.uint32)
+        lp, lt = np.zeros(nl, np.uint32), np.zeros(nl, np.uint64)
+        b = out.batch
+        for dst, src in ((src_off, b.src_off), (t, b.send_time), (d, b.dst_host), (p, b.payload), (sp, out.sent_pkt),
+                         (loc_off, out.loc_off), (lp, out.loc_pkt), (lt, out.loc_time)):
+            if dst.nbytes:
+                N.check(self.eng.lib.shd_copy_to_host(self.eng.ctx, N.ptr(dst), C.c_void_p(src), dst.nbytes),
+                        "shd_copy_to_host")
+        return Sent(src_off, t, d, p, sp, loc_off, lp, lt, out.n_stored, out.next_task_time)
+
+    def state(self, host: int) -> dict:
+        """One host: ``task_time`` (None: Idle), ``cached`` ((pkt, size) or None), ``queue_len``,
+        ``head_pkt`` (the lowest priority queued, None: empty) and the bucket as
+        ``TokenBuckets.state`` (None: no bucket)."""
+        task, has, cp, cs = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        ql, hp, b = C.c_uint32(0), C.c_uint32(0), N.TbState()
+        N.check(self.eng.lib.shd_outbound_get_state(self.eng.ctx, int(host), C.byref(task), C.byref(has),
+                                                    C.byref(cp), C.byref(cs), C.byref(ql), C.byref(hp), C.byref(b)),
+                "shd_outbound_get_state")
+        bucket = {k: int(getattr(b, k)) for k, _ in N.TbState._fields_} if b.capacity else None
+        return {"task_time": None if task.value == IDLE else task.value,
+                "cached": (cp.value, cs.value) if has.value else None, "queue_len": ql.value,
+                "head_pkt": None if hp.value == NO_PKT else hp.value, "bucket": bucket}
