@@ -126,22 +126,22 @@ __device__ __forceinline__ void relax_node(uint32_t u, uint32_t gl, uint64_t* la
     }
 }
 
-// Padded arc lists (pruned dense graphs, prune_rows): every node's list is a multiple of
-// kArcPad slots, the tail filled with no-op arcs {scratch label V + i, lat 0, q 0} whose
+// Padded arc lists (pruned dense graphs, prune_rows / prune_rows2): every node's list is a multiple
+// of the pad width ArcView::pad (64 or 32 slots, a multiple of the group step G x R), the tail
+// filled with no-op arcs {scratch label V + i, lat 0, q 0} whose
 // candidate (lu, 1.0f) meets a scratch label holding 0.  The group then loads its G x R slots
 // at immediate offsets from one address, with no clamp, liveness test or per-arc select, and
 // the u32 overflow test is one compare per node: a label above lat_guard (2^32 - 2 - the
 // largest arc latency) flags the build for the wide rerun before any add can wrap.  The
 // kernel is issue-bound (C2 PMC: VALU pipe ~70% busy), so these per-arc instructions are the
 // cost that matters.
-constexpr uint32_t kArcPad = 64;
 template <int G, int R, bool CACHE>
 __device__ __forceinline__ void relax_node_pad(uint32_t u, uint32_t gl, uint64_t* lab, uint32_t* bits,
                                                const uint2* rng, const uint32_t* __restrict__ abeg,
                                                const uint32_t* __restrict__ aend,
                                                const uint4* __restrict__ arcs, uint32_t lat_guard,
                                                bool& ovf, bool& dirty, uint32_t& mnext) {
-    static_assert(kArcPad % (G * R) == 0, "a padded list holds whole G x R steps");
+    static_assert(G * R == 32 || G * R == 64, "a padded list holds whole G x R steps");
     const uint64_t ku = lab[u];
     const uint32_t lu = key_lat(ku);
     if (lu > lat_guard) ovf = true;
@@ -619,7 +619,7 @@ __device__ __forceinline__ void sssp_row(
                 for (uint32_t t = 0; t < qn; t += NG) {
                     const uint32_t qi = t + grp;
                     if (qi >= qn) continue;
-                    if constexpr (PADR != 0) {   // padded lists: a whole 64-slot list per group step
+                    if constexpr (PADR != 0) {   // padded lists: G x PADR slots (a whole 32-slot list) per group step
                         relax_node_pad<G, PADR, CACHE>(q[qi], gl, lab, bits, rng, abeg, aend, arcs, lat_guard,
                                                        ovf, dirty, mnext);
                     } else {
@@ -897,7 +897,7 @@ __device__ __forceinline__ void sssp_row(
 }
 
 // Kernel 1: one workgroup per source row, labels (8 B/node) and the arc ranges in LDS.
-// PADR = 8: padded arc lists (prune_rows), relax_node_pad with 8 arcs per lane per step.
+// PADR = 8, 4: padded arc lists (prune_rows, prune_rows2), relax_node_pad with PADR arcs per lane per step.
 template <int BLOCK, int G, int R, bool CACHE, int PADR, bool FLATL = false>
 __global__ __launch_bounds__(BLOCK) void sssp_lds_group(
     const uint32_t* __restrict__ abeg, const uint32_t* __restrict__ aend,
@@ -1071,6 +1071,7 @@ __device__ __forceinline__ uint32_t dense_lat(const uint32_t* __restrict__ Wl, u
     else return Wl[(size_t)x * V + v];
 }
 
+constexpr uint32_t kPad1 = 64, kPad2 = 32;   // list padding in slots: prune_rows, prune_rows2
 template <int BLOCK, int K, bool DCSR = false, int VB = 4, int KB = 8, bool CMP = false, int PB = 8>
 __global__ __launch_bounds__(BLOCK) void prune_rows(
     const uint32_t* __restrict__ Wl, const float* __restrict__ Wp, uint32_t V,
@@ -1381,18 +1382,20 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
     }
     __syncthreads();
     PR_MARK(4);
-    // each list is padded to kArcPad slots with no-op arcs for relax_node_pad (scratch label
+    // each list is padded to kPad1 slots with no-op arcs for relax_node_pad (scratch label
     // V + i, lat 0, q 0: candidate (lu, 1.0f) against a scratch label holding 0).  Row u's list
-    // starts at u * roundup(V, kArcPad): the 1000 workgroups of C2 finish together, and one
+    // starts at u * roundup(V, kPad1): the 1000 workgroups of C2 finish together, and one
     // shared cursor (rows packed in arrival order) serialised their atomics at the end of the
     // kernel; the slots a sweep touches are the same lines either way.
-    const uint32_t n = cnt[0], np = (n + kArcPad - 1) / kArcPad * kArcPad;
+    // (at least one block of slots, also for an empty list: prune_rows2 reads the first kPad1 slots
+    // of other rows' lists without their lengths)
+    const uint32_t n = cnt[0], np = max((n + kPad1 - 1) / kPad1 * kPad1, kPad1);
 #ifdef SHD_PRUNE_CURSOR   // (tuning A/B: rows packed by one atomic cursor)
     if (tid == 0) cnt[1] = atomicAdd(cursor, np);
     __syncthreads();
     const uint32_t at = cnt[1];
 #else
-    const uint32_t at = u * ((V + kArcPad - 1) / kArcPad * kArcPad);
+    const uint32_t at = u * ((V + kPad1 - 1) / kPad1 * kPad1);
 #endif
     for (uint32_t i = tid; i < np; i += BLOCK)
         parcs[at + i] = i < n ? kept[i] : make_uint4(V + (i & 63u), 0u, 0u, 0u);
@@ -1408,6 +1411,142 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
         g_prune_prof[u * 8 + 7] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
+}
+
+// Second prune stage (prune_rows2): a 3-hop test over the lists that prune_rows kept, one
+// workgroup per row u.  The 2-hop prune stops at ~48 arcs per node on C2 because its survivors
+// need 3-hop detours to fall; over the dense matrix that test costs as much as the prune, over
+// the kept lists it is ~2,400 pairs per row:
+//   d2[y] = min(lat(u, y) if (u, y) is kept, min over kept x of lat(u, x) + lat(x, y) with
+//           (x, y) kept by row x)                                   -- a walk u -> x -> y
+//   (u, v) is dropped iff some y in kept(v), y != u, y != v, has d2[y] + lat(y, v) < lat(u, v),
+//   lat(y, v) read from the dense matrix (the arc y -> v itself: kept(v) only names candidates,
+//   and on a directed graph lat(v, y) is another number).
+// Soundness: every compared detour is a walk u -> (x ->) y -> v of real arcs with their original
+// latencies (the stage-1 lists hold arcs of the graph unchanged, Wl holds the graph's arcs).  An
+// arc with a strictly shorter walk between its ends lies on no shortest-latency path, and the loss
+// is chosen only among shortest-latency paths, so the tables do not see it.  A tight arc
+// (lat(u, v) = d(u, v)) has no strictly shorter walk, so it is never dropped -- whatever other
+// rows drop at the same time: the test reads only stage-1 lists and the matrix, never a
+// stage-2 list, and every shortest path is made of tight arcs alone.  Ties (<, strictly) keep
+// the arc.  Any candidate set is sound; it only decides how much is dropped.
+// The sums: lat(u, x) + lat(x, y) is guarded as in prune_rows (a wrapped or +inf sum is no
+// detour); the three-term sum is formed in 64 bits, so it cannot wrap into a "shorter" walk.
+// +inf entries (no arc) are never added.
+// Memory trips: a stage-1 list starts at its row's fixed offset and its first kPad1 slots are
+// always written (pads name a node >= V), so the kernel needs no list length but its own: one
+// trip for kept(u), one for the first 64 slots of every kept node's list (wave w takes lists w,
+// w + 8, ..., a lane per slot), one for
+// the lat(y, v) gathers of the pairs whose d2[y] is below lat(u, v), and the list write.
+// Bounded work: 64 lists x 64 slots = 4,096 pairs at most (C2: ~2,400).  A row of more than
+// kP2MaxKept = 64 kept arcs (heavily tied graphs, where stage 1 prunes nothing; a handful of C2
+// rows) is copied through unchanged, and a kept node's list of 64 arcs or more (its slot 63 is no
+// pad) names no candidates: both rules depend on list lengths only, never on the order in which
+// stage 1's atomics filled a list, so they are the same on every run.  The surviving set is the
+// same on every run (d2 is a minimum, the drop flags are idempotent); survivors keep their
+// stage-1 order.
+// Lists are padded to kPad2 = 32 slots with the same no-op arcs as stage 1, at the same fixed
+// per-row offset in a second buffer (the kernel reads other rows' stage-1 lists while it runs).
+constexpr uint32_t kP2MaxKept = 64;   // C2: 48.5 arcs per row, 66 at most
+constexpr int kP2Block = 512, kP2Half = 8;   // 8 waves x kP2Half lists = the 64 lists tested
+static size_t prune2_lds_bytes(uint32_t V) { return (size_t)kP2MaxKept * 16 + (size_t)kP2MaxKept * 4 + (size_t)V * 4; }
+template <bool DCSR>
+__global__ __launch_bounds__(kP2Block) void prune_rows2(
+    const uint32_t* __restrict__ Wl, uint32_t V, const uint32_t* __restrict__ beg1,
+    const uint32_t* __restrict__ end1, const uint4* __restrict__ arcs1, uint32_t* __restrict__ pbeg,
+    uint32_t* __restrict__ pend, uint4* __restrict__ parcs) {
+    static_assert((kP2Block / 64) * kP2Half == 64 && kP2MaxKept == 64 && kPad1 == 64, "64 lists, a lane per slot");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* ku = reinterpret_cast<uint4*>(smem);                      // kept(u), as stage 1 wrote it
+    uint32_t* drop = reinterpret_cast<uint32_t*>(ku + kP2MaxKept);   // [kP2MaxKept] arc falls
+    uint32_t* d2 = drop + kP2MaxKept;                                // [V] 2-hop row
+    const uint32_t u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t stride = (V + kPad1 - 1) / kPad1 * kPad1;
+    const uint32_t at = u * stride;   // the row's fixed offset, in both buffers
+    const uint4* mine = arcs1 + at;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < kPad1) a = mine[tid];   // (always written: rides the same trip as the length)
+    const uint32_t n = end1[u] - beg1[u];
+    if (n > kP2MaxKept) {   // too long a list (too much work): the stage-1 list as it is
+        const uint32_t np = (n + kPad2 - 1) / kPad2 * kPad2;
+        for (uint32_t i = tid; i < np; i += kP2Block)
+            parcs[at + i] = i < n ? mine[i] : make_uint4(V + (i & 63u), 0u, 0u, 0u);
+        if (tid == 0) {
+            pbeg[u] = at;
+            pend[u] = at + n;
+        }
+        return;
+    }
+    if (tid < n) ku[tid] = a;
+    if (tid < kP2MaxKept) drop[tid] = 0u;
+    for (uint32_t v = tid; v < V; v += kP2Block) d2[v] = kLat32Inf;
+    __syncthreads();
+    // pair (list j = kept(u)[j], slot): {y, lat(x, y)}; a pad slot (y >= V) or a list past n: none
+    auto load_half = [&](uint32_t h, uint2* pr) {
+#pragma unroll
+        for (int k = 0; k < kP2Half; ++k) {
+            const uint32_t j = h * 64 + (uint32_t)k * (kP2Block / 64) + wave;   // wave-uniform
+            pr[k] = make_uint2(0xFFFFFFFFu, kLat32Inf);
+            if (j < n) pr[k] = *reinterpret_cast<const uint2*>(arcs1 + (size_t)ku[j].x * stride + lane);
+            // a list of 64 arcs or more (slot 63 holds an arc) is cut off by the block: not used
+            if ((uint32_t)__shfl((int)pr[k].x, 63) < V) pr[k] = make_uint2(0xFFFFFFFFu, kLat32Inf);
+        }
+    };
+    auto build_half = [&](uint32_t h, const uint2* pr) {   // d2 over the walks u -> x -> y
+#pragma unroll
+        for (int k = 0; k < kP2Half; ++k) {
+            const uint32_t j = h * 64 + (uint32_t)k * (kP2Block / 64) + wave;
+            if (j >= n) continue;
+            const uint32_t l1 = ku[j].y, t = l1 + pr[k].y;
+            if (pr[k].x < V && pr[k].x != u && pr[k].y != kLat32Inf && t >= l1 && t != kLat32Inf)
+                atomicMin(&d2[pr[k].x], t);
+        }
+    };
+    auto test_half = [&](uint32_t h, const uint2* pr) {   // (u, v = list j's node) against u ~> y -> v
+        uint32_t lyv[kP2Half], dy[kP2Half];
+#pragma unroll
+        for (int k = 0; k < kP2Half; ++k) {
+            const uint32_t j = h * 64 + (uint32_t)k * (kP2Block / 64) + wave;
+            lyv[k] = kLat32Inf;
+            dy[k] = kLat32Inf;
+            if (j >= n) continue;
+            const uint32_t y = pr[k].x, v = ku[j].x;
+            if (y >= V || y == u || y == v) continue;
+            const uint32_t d = d2[y];
+            // (a walk no shorter than the arc before its last step cannot beat it: no load)
+            if (d != kLat32Inf && d < ku[j].y) {
+                dy[k] = d;
+                lyv[k] = dense_lat<DCSR>(Wl, V, y, v);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kP2Half; ++k) {
+            const uint32_t j = h * 64 + (uint32_t)k * (kP2Block / 64) + wave;
+            if (j < n && lyv[k] != kLat32Inf && dy[k] != kLat32Inf && (uint64_t)dy[k] + lyv[k] < (uint64_t)ku[j].y)
+                drop[j] = 1u;
+        }
+    };
+    // the pairs stay in registers through both passes
+    uint2 pr0[kP2Half];
+    load_half(0, pr0);
+    if (tid < n) atomicMin(&d2[ku[tid].x], ku[tid].y);   // the direct arcs u -> y
+    build_half(0, pr0);
+    __syncthreads();
+    test_half(0, pr0);
+    __syncthreads();
+    // survivors in stage-1 order (wave 0), then the pad slots
+    if (tid < 64) {
+        const bool k0 = lane < n && drop[lane] == 0u;
+        const uint64_t b0 = __ballot(k0);
+        const uint32_t n2 = (uint32_t)__popcll(b0);
+        if (k0) parcs[at + (uint32_t)__popcll(b0 & ((1ull << lane) - 1ull))] = ku[lane];
+        const uint32_t np = (n2 + kPad2 - 1) / kPad2 * kPad2;
+        if (n2 + lane < np) parcs[at + n2 + lane] = make_uint4(V + ((n2 + lane) & 63u), 0u, 0u, 0u);
+        if (lane == 0) {
+            pbeg[u] = at;
+            pend[u] = at + n2;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1939,7 +2078,7 @@ struct ArcView {
     const uint32_t *beg, *end;
     const uint4* arcs;
     uint64_t n_arcs;
-    bool padded = false;   // lists padded to kArcPad slots with no-op arcs (prune_rows)
+    uint32_t pad = 0;      // lists padded to this many slots with no-op arcs (prune_rows 64, prune_rows2 32; 0: not)
     const uint32_t* used = nullptr;   // a relabelled copy (prepare_spread): the used nodes' new ids
 };
 
@@ -1952,7 +2091,7 @@ static void launch_group(shd_ctx* ctx, const ArcView& A, uint32_t rb, uint32_t r
     // padded lists: labels stay below 2^32 - 1 while lu <= guard (0 = unpadded path)
     const uint64_t guard = (uint64_t)kLat32Inf - 1 - P.max_arc_lat;
     const uint32_t lat_guard =
-        A.padded && delta != kLat32Inf && !seed && P.max_arc_lat < kLat32Inf - 1 &&
+        A.pad != 0 && delta != kLat32Inf && !seed && P.max_arc_lat < kLat32Inf - 1 &&
                 ctx->knobs.get(K_SSSP_NO_PAD, 0) != 1
             ? (uint32_t)std::max<uint64_t>(guard, 1)
             : 0u;
@@ -1961,9 +2100,15 @@ static void launch_group(shd_ctx* ctx, const ArcView& A, uint32_t rb, uint32_t r
     auto* stats = ctx->stats_on ? reinterpret_cast<unsigned long long*>(ctx->g_flags.as<char>() + 32) : nullptr;
     hipEvent_t e0 = ctx->time_now ? ctx->ev[2] : nullptr, e1 = ctx->time_now ? ctx->ev[3] : nullptr;
     const uint32_t* usedp = A.used ? A.used : P.used_ident ? nullptr : (const uint32_t*)ctx->g_used.as<uint32_t>();
-    if constexpr (kArcPad % (G * 8) == 0) {
+    if constexpr (G == 4 || G == 8) {
         if (lat_guard) {
-            hipExtLaunchKernelGGL(sssp_lds_group<BLOCK, G, R, CACHE, 8>, dim3(re - rb), dim3(BLOCK), (uint32_t)lds,
+            // a group step covers G x PADR slots: a whole list of 64 (G = 8) or 32 slots (G = 4 with 8
+            // arcs per lane, G = 8 with 4), or half a 64-slot list (G = 4); wider groups take the
+            // unpadded path below
+            auto kern = sssp_lds_group<BLOCK, G, R, CACHE, 8>;
+            if constexpr (G == 8)
+                if (A.pad == 32) kern = sssp_lds_group<BLOCK, G, R, CACHE, 4>;
+            hipExtLaunchKernelGGL(kern, dim3(re - rb), dim3(BLOCK), (uint32_t)lds,
                                   ctx->stream, e0, e1, 0u, A.beg, A.end, A.arcs, P.V, usedp, P.n_used, rb,
                                   (const uint64_t*)ctx->g_diag_lat.as<uint64_t>(),
                                   (const float*)ctx->g_diag_loss.as<float>(), d_lat, d_loss, flags, unreach, delta,
@@ -1974,7 +2119,7 @@ static void launch_group(shd_ctx* ctx, const ArcView& A, uint32_t rb, uint32_t r
     // edge-parallel expansion (expand_flat) for sparse graphs whose hubs would idle a node
     // group's wave (SHD_SSSP_LFLAT=1), when its per-wave scratch fits beside the rest
     const size_t flat_off = (lds + 15) & ~(size_t)15, flat_bytes = (size_t)(BLOCK / 64) * kFlatWords * 4;
-    const bool flatl = !A.padded && !seed && delta != kLat32Inf && ctx->knobs.get(K_SSSP_LFLAT, 0) == 1 &&
+    const bool flatl = A.pad == 0 && !seed && delta != kLat32Inf && ctx->knobs.get(K_SSSP_LFLAT, 0) == 1 &&
                        flat_off + flat_bytes <= ctx->max_lds;
     auto kern = flatl ? sssp_lds_group<BLOCK, G, R, CACHE, 0, true> : sssp_lds_group<BLOCK, G, R, CACHE, 0, false>;
     hipExtLaunchKernelGGL(kern, dim3(re - rb), dim3(BLOCK), (uint32_t)(flatl ? flat_off + flat_bytes : lds),
@@ -2023,6 +2168,9 @@ static shd_status run_sssp(shd_ctx* ctx, const ArcView& A, uint32_t rb, uint32_t
     // G lanes x R arcs (R = 4 below G = 32) per node; measured best on C2 (pruned, ~48 arcs
     // per node) at G = 8 and on C3 (BA, ~6 arcs per node) at G = 4
     uint32_t G = deg >= 64 ? 16 : deg >= 24 ? 8 : 4;
+    // 32-slot padded lists (prune_rows2, ~21 arcs per node on C2): G = 8 with 4 arcs per lane, equal
+    // or ~1 us ahead of G = 4 with 8 (54 against 72 VGPRs; DESIGN 4, routing item 2)
+    if (A.pad == kPad2) G = 8;
     G = ctx->knobs.get(K_SSSP_G, G);          // tuning overrides (results are identical)
     // Workgroup shape: once a source's labels need most of the LDS, one 1024-thread workgroup
     // per CU (the LDS arc-range cache is dropped when it no longer fits).  Otherwise rows per CU
@@ -2198,17 +2346,25 @@ constexpr uint32_t kPruneK = 32;
 constexpr uint32_t kPruneMaxV = 4096;
 constexpr uint32_t kBlockedMaxV = 16384;   // closure matrix <= 1 GiB
 
-// Dense arc matrix + k-nearest 2-hop prune over all V rows -> pruned arc lists (row stride V).
+// Dense arc matrix + k-nearest 2-hop prune over all V rows -> pruned arc lists (row stride V),
+// then the 3-hop stage over those lists (prune_rows2; SHD_PRUNE_STAGE2=0: stage 1 alone, 64-slot lists).
 static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
     PreparedGraph& P = ctx->prep;
     hipStream_t s = ctx->stream;
     const uint32_t V = P.V;
     const uint64_t nn = (uint64_t)V * V;
-    SHD_TRY(ctx->g_prune_dst.ensure((nn + (uint64_t)V * kArcPad) * 16));   // + list padding
-    SHD_TRY(ctx->g_prune_cnt.ensure((size_t)V * 8 + 16));
+#ifdef SHD_PRUNE_CURSOR   // (rows packed by a cursor: no fixed offsets for prune_rows2 to read)
+    const bool stage2 = false;
+#else
+    const bool stage2 = ctx->knobs.get(K_PRUNE_STAGE2, 1) != 0;
+#endif
+    SHD_TRY(ctx->g_prune_dst.ensure((nn + (uint64_t)V * kPad1) * 16));   // + list padding
+    SHD_TRY(ctx->g_prune_cnt.ensure((size_t)V * 16 + 16));
     uint32_t* pbeg = ctx->g_prune_cnt.as<uint32_t>();
     uint32_t* pend = pbeg + V;
     uint32_t* cursor = pend + V;
+    uint32_t* pbeg2 = cursor + 4;   // the final lists' ranges (stage 2)
+    uint32_t* pend2 = pbeg2 + V;
     uint4* pa = ctx->g_prune_dst.as<uint4>();
     uint32_t* flags = ctx->g_flags.as<uint32_t>();
     const uint32_t Kr = ctx->knobs.get(K_PRUNE_K, kPruneK);   // tuning: detour nodes per row (same output tables)
@@ -2221,7 +2377,8 @@ static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
     // bins from the graph's largest arc latency instead of each row's (SHD_PRUNE_SHAPE_SH=0: per row)
     const uint32_t gbits = 64u - (uint32_t)__builtin_clzll(std::max<uint64_t>(std::min<uint64_t>(P.max_arc_lat, kLat32Inf - 1), 1));
     const uint32_t shg = ctx->knobs.get(K_PRUNE_SHAPE_SH, 1) ? (gbits > 8 ? gbits - 8 : 0) : 0xFFFFFFFFu;
-    if (P.dense_rows && !ctx->knobs.on(K_PRUNE_DENSE_BUILD)) {
+    const bool dcsr = P.dense_rows && !ctx->knobs.on(K_PRUNE_DENSE_BUILD);
+    if (dcsr) {
         // the CSR is the dense matrix (complete graph, arcs in index order): prune straight from it
         const uint32_t* Wl = ctx->g_lat.as<uint32_t>();
         const float* Wp = ctx->g_aux.as<float>();
@@ -2243,7 +2400,18 @@ static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
         else prune_rows<512, 32, false, 2, 8, true, 12><<<V, 512, plds_c, s>>>(Wl, Wp, V, pbeg, pend, pa, cursor, flags, shg);
     }
     SHD_HIP(hipGetLastError());
-    *out = ArcView{pbeg, pend, ctx->g_prune_dst.as<uint4>(), 0, true};
+    *out = ArcView{pbeg, pend, ctx->g_prune_dst.as<uint4>(), 0, kPad1};
+    if (!stage2) return SHD_OK;
+    // stage 2 reads other rows' stage-1 lists while it runs: its lists go to a second buffer, each
+    // at its row's stage-1 offset (a final list is no longer than the stage-1 one)
+    const uint64_t stride = ((uint64_t)V + kPad1 - 1) / kPad1 * kPad1;
+    SHD_TRY(ctx->g_prune_dst2.ensure(std::max<uint64_t>(V * stride, 1) * 16));
+    uint4* pa2 = ctx->g_prune_dst2.as<uint4>();
+    const size_t lds2 = prune2_lds_bytes(V);
+    if (dcsr) prune_rows2<true><<<V, kP2Block, lds2, s>>>(ctx->g_lat.as<uint32_t>(), V, pbeg, pend, pa, pbeg2, pend2, pa2);
+    else prune_rows2<false><<<V, kP2Block, lds2, s>>>(ctx->g_labels.as<uint32_t>(), V, pbeg, pend, pa, pbeg2, pend2, pa2);
+    SHD_HIP(hipGetLastError());
+    *out = ArcView{pbeg2, pend2, pa2, 0, kPad2};
     return SHD_OK;
 }
 
@@ -2256,6 +2424,7 @@ static shd_status count_kept(shd_ctx* ctx, const ArcView& A) {
     for (size_t i = 0; i < b.size(); i++) k += e[i] - b[i];
     ctx->info.arcs_kept = k;
     ctx->prep.pruned_arcs = k;
+    ctx->prep.pruned_pad = A.pad;
     return SHD_OK;
 }
 
@@ -2499,7 +2668,8 @@ shd_status routing_run_impl(shd_ctx* ctx, uint32_t algo, uint32_t rb, uint32_t r
             SHD_TRY(run_prune(ctx, &A));
             // the kept-arc count steers the lane-group width: counted once per prepared graph,
             // before its first SSSP launch, so every build (the first too) runs the same kernel
-            if (P.pruned_arcs == 0) SHD_TRY(count_kept(ctx, A));
+            // (again if SHD_PRUNE_STAGE2 changed between two builds of one prepared graph)
+            if (P.pruned_arcs == 0 || P.pruned_pad != A.pad) SHD_TRY(count_kept(ctx, A));
             A.n_arcs = P.pruned_arcs;
         }
         bool ovf = false;
@@ -2568,12 +2738,12 @@ shd_status routing_run_impl(shd_ctx* ctx, uint32_t algo, uint32_t rb, uint32_t r
 
 // Test hook (not part of the ABI header): the vector registers of the shipped SSSP kernels,
 // which sit at the budgets their residency needs (tests/test_routing_gpu.py): 0 = C4's global-
-// label kernel (two 512-thread slots per CU: <= 128), 1 = C2's padded-list kernel (four 256-thread
-// workgroups per CU: <= 128), 2 = C3's 1024-thread kernel (<= 128)
+// label kernel (two 512-thread slots per CU: <= 128), 1 = C2's padded-list kernel (32-slot lists,
+// G = 8 x 4 arcs per lane; four 256-thread workgroups per CU: <= 128), 2 = C3's 1024-thread kernel (<= 128)
 extern "C" int shd_debug_kernel_vgprs(int which) {
     hipFuncAttributes at{};
     const void* f = which == 0   ? reinterpret_cast<const void*>(&shd::sssp_global_group<512, 4, 4, true>)
-                    : which == 1 ? reinterpret_cast<const void*>(&shd::sssp_lds_group<256, 8, 4, true, 8, false>)
+                    : which == 1 ? reinterpret_cast<const void*>(&shd::sssp_lds_group<256, 8, 4, true, 4, false>)
                                  : reinterpret_cast<const void*>(&shd::sssp_lds_group<1024, 4, 2, false, 0, false>);
     return hipFuncGetAttributes(&at, f) == hipSuccess ? at.numRegs : -1;
 }
