@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 5
+#define SHD_ABI_VERSION 6
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -465,6 +465,9 @@ shd_status shd_equeue_advance(shd_ctx* ctx, const shd_relay_out* d_batch, uint64
  * output (with the caller's status array), then to shd_equeue_advance, which adopts the batch as
  * a stored run without copying any of it.  Valid until that advance (or the next call). */
 shd_status shd_equeue_batch_buffers(shd_ctx* ctx, uint64_t max_events, shd_relay_out* out);
+/* The number the next non-NULL batch passed to shd_equeue_advance will get in its events' tags
+ * (batch numbers count the non-NULL batches since shd_equeue_setup). */
+shd_status shd_equeue_next_batch(shd_ctx* ctx, uint64_t* batch);
 /* Host copies of the last advance's popped events (any pointer may be NULL). */
 shd_status shd_equeue_copy_popped(shd_ctx* ctx, uint32_t* off, uint64_t* deliver, uint32_t* src,
                                   uint64_t* seq, uint64_t* tag);
@@ -738,6 +741,11 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
                                 shd_batch* d_batch_out, const uint32_t** sent_pkt,
                                 const uint32_t** loc_off, const uint32_t** loc_pkt, const uint64_t** loc_time,
                                 uint64_t* n_local, uint64_t* n_stored, uint64_t* next_task_time);
+/* The total sizes of the last advance's batch (device, engine-owned, valid until the next advance):
+ * d_size[i] = the size the offer of batch entry i carried -- with *sent_pkt what shd_ledger_record
+ * keeps for the destination side.  NULL before the first advance.  SHD_ERR_STATE wherever
+ * shd_outbound_get_state returns it. */
+shd_status shd_outbound_sent_sizes(shd_ctx* ctx, const uint32_t** d_size);
 /* One host's state (any pointer may be NULL): *task_time UINT64_MAX = Idle; the cached packet;
  * the queue's length and the packet at its head (the lowest priority; UINT32_MAX: empty); the
  * bucket in the struct of shd_tb_get_state (pending_until = the task time, 0 when Idle).
@@ -746,6 +754,94 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
 shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_time, uint32_t* has_cached,
                                   uint32_t* cached_pkt, uint32_t* cached_size, uint32_t* queue_len,
                                   uint32_t* head_pkt, shd_tb_state* bucket);
+
+/* ---------------------------------------------------------------------------------------
+ * Packet ledger: what joins the event queues to the inbound stage on the device.  A popped event
+ * carries its tag, (batch number << 32) | index in that batch; shd_inbound_advance wants the
+ * packet's total size and the caller's packet id.  The ledger keeps each batch's (size, id) per
+ * packet on the device from the relay round that sent it until its last event has popped, and
+ * gathers a window's popped tags into the two arrays the inbound stage takes.  No reference
+ * counterpart: the reference's events own their packets.
+ *
+ * One arena of 8-byte entries, a batch one contiguous slice; space comes back in batch order: a
+ * batch that drains before an older one stays held until the older one is gone.  The batches held
+ * span at most max_live_batches consecutive batch numbers (numbers never recorded in between
+ * count).  The arena grows with its contents kept, in a record only.
+ * ------------------------------------------------------------------------------------- */
+
+/* (Re)create an empty ledger.  max_live_batches 0 = 1024; above 4096: SHD_ERR_INVALID.  Also starts
+ * the window calls below over (the next one is an open, no relay output is pending). */
+shd_status shd_ledger_setup(shd_ctx* ctx, uint32_t max_live_batches);
+/* Keep (d_size[i], d_pkt[i]), i < n_packets (device arrays), under batch number `batch`
+ * (shd_equeue_next_batch before the batch's advance); n_live of them will pop
+ * (shd_relay_out.n_sent).  Batch numbers strictly increase.  n_live == 0 stores nothing.  No host
+ * synchronisation: the two arrays are read on the context's stream and must stay as they are until
+ * work queued behind the call has finished (engine-owned arrays such as shd_outbound_advance's do:
+ * the call that replaces them is queued on the same stream).  SHD_ERR_INVALID before anything runs, the ledger as it was: a NULL array with
+ * n_packets > 0, a batch number not above the last one recorded, n_live > n_packets, or a batch
+ * max_live_batches or more numbers above the oldest one held. */
+shd_status shd_ledger_record(shd_ctx* ctx, uint64_t batch, const uint32_t* d_size, const uint32_t* d_pkt,
+                             uint64_t n_packets, uint64_t n_live);
+/* d_tag[n] as shd_equeue_out.tag lies on the device -> engine-owned device arrays (*d_size)[n],
+ * (*d_pkt)[n], valid until the next gather: what shd_inbound_advance takes.  Lowers each named
+ * batch's live count; a batch at 0 is retired (the call ends with one read-back of the status and
+ * the live counts: its one host synchronisation).  SHD_ERR_INVALID, refused by checks in the
+ * kernel before any index is used for a load: a tag whose batch is not held or has no live event
+ * left, an index >= its batch's n_packets, a batch popped more often than its n_live.  Such an
+ * event has UINT32_MAX in both outputs, the other events of the call are right (of an overdrawn
+ * batch at least the surplus events are refused; which ones is not defined), and every later
+ * ledger call returns SHD_ERR_STATE until shd_ledger_setup.  A NULL d_tag with n > 0 is
+ * SHD_ERR_INVALID before anything runs. */
+shd_status shd_ledger_gather(shd_ctx* ctx, const uint64_t* d_tag, uint64_t n, const uint32_t** d_size,
+                             const uint32_t** d_pkt);
+/* Batches with a live event, their live events, the arena entries held (the sum of n_packets from
+ * the oldest batch held to the newest) and the oldest batch held (UINT64_MAX: none).  Any pointer
+ * may be NULL.  After every shd_window_open live_events equals the queues' n_pending. */
+shd_status shd_ledger_stats(shd_ctx* ctx, uint64_t* live_batches, uint64_t* live_events, uint64_t* entries_held,
+                            uint64_t* oldest_batch);
+
+/* ---------------------------------------------------------------------------------------
+ * The scheduling window in two calls.  The inbound records of window k come first -- a delivered
+ * segment makes its socket answer -- and the CPU turns them into offers of the same window, so a
+ * window is
+ *   shd_window_open    shd_equeue_advance (merging the relay output the last close left in the
+ *                      slot shd_equeue_batch_buffers lent; none: NULL) -> shd_ledger_gather on the
+ *                      popped tags -> shd_inbound_advance on the popped off / deliver as they lie
+ *                      and the gathered arrays
+ *   [CPU: sockets, applications; this window's offers]
+ *   shd_window_close   shd_outbound_advance -> if anything was sent shd_relay_round_device (device
+ *                      draws) into the lent queue buffers and an engine-owned status array ->
+ *                      shd_ledger_record(shd_equeue_next_batch, the batch's sizes and ids,
+ *                      n_packets, n_sent)
+ * with no packet data crossing the host.  Every event of a batch has deliver >= its window_end, so
+ * merging it at the next open pops exactly what merging it at once would have.  The relay output
+ * is not merged by the close: shd_round_window already counts its earliest deliver time; the
+ * caller folds min(*inbound_next_task, *outbound_next_task) into cpu_next_event_time as with the
+ * separate calls.  Outputs are the stages' (engine-owned device arrays, any pointer may be NULL):
+ * the open's are shd_inbound_advance's plus the queues' n_popped / n_pending / next_time; the
+ * close's are shd_outbound_advance's sent_pkt and local deliveries, *sent_status (SHD_PKT_* per
+ * batch entry), *n_batch (batch entries), *n_events (of them sent: events for the queues) and
+ * *min_deliver (shd_relay_out.min_deliver; UINT64_MAX: none).
+ * SHD_ERR_STATE, nothing changed: relay, queues, runahead, both stages and the ledger are not all
+ * set up for the same host count with first_host 0, or the context is under a communicator of
+ * more than one rank (sharded windows are not covered: a received event's index names the sender
+ * rank's batch, which the receiver's ledger does not hold); a close without its open, two opens
+ * in a row.  SHD_ERR_INVALID before anything runs: a close whose window_end is not its open's, or
+ * a close while the ledger already spans max_live_batches batch numbers.  Otherwise the statuses
+ * of the stages, as they return them.
+ * ------------------------------------------------------------------------------------- */
+shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap_end,
+                           const uint32_t** out_off, const uint32_t** out_pkt, const uint64_t** out_time,
+                           const uint8_t** out_kind, uint64_t* n_out, uint64_t* n_stored,
+                           uint64_t* inbound_next_task, uint64_t* n_popped, uint64_t* n_pending,
+                           uint64_t* queue_next_time);
+shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time, const uint64_t* d_prio,
+                            const uint32_t* d_size, const uint32_t* d_payload, const uint32_t* d_dst,
+                            const uint32_t* d_pkt, uint64_t n_offers, uint64_t window_end, uint64_t sim_end,
+                            uint64_t bootstrap_end, const uint32_t** sent_pkt, const uint8_t** sent_status,
+                            uint64_t* n_batch, uint64_t* n_events, const uint32_t** loc_off,
+                            const uint32_t** loc_pkt, const uint64_t** loc_time, uint64_t* n_local,
+                            uint64_t* n_stored, uint64_t* outbound_next_task, uint64_t* min_deliver);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, "csrc", f) for f in ("routing.hip", "blocked.hip", "relay.hip", "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue.hip",
                                                 "hosts.cpp", "rounds.hip", "flush.hip", "inbound.hip",
-                                                "outbound.hip")]
+                                                "outbound.hip", "ledger.hip", "window.cpp")]
 OUT = os.path.join(HERE, "libshd_accel.so")
 OBJ = os.path.join(HERE, "build", "obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

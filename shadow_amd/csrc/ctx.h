@@ -6,6 +6,7 @@
 #include "comm.h"
 #include "common.h"
 #include "knobs.h"
+#include "ledger_book.h"
 
 namespace shd {
 
@@ -154,15 +155,39 @@ struct OutboundState {
     DevBuf tb;                     // TbRelay per host
     DevBuf rl;                     // OutRelay per host: task time, the queue's first packet, ring head / count, the cached packet
     DevBuf cnt, nsent, nloc;       // [n_hosts + 1] record region bounds -> offsets; SENT / LOCAL records written
-    DevBuf r_pkt, r_time, r_dst, r_pay;    // the records in their per-host regions (SENT front, LOCAL back)
-    DevBuf src_off, b_time, b_dst, b_pay, b_pkt;   // the last advance's batch (shd_batch) and its packet ids
+    DevBuf r_pkt, r_time, r_dst, r_pay, r_size;   // the records in their per-host regions (SENT front, LOCAL back)
+    DevBuf src_off, b_time, b_dst, b_pay, b_pkt, b_size;   // the last advance's batch (shd_batch), its packet ids and total sizes
     DevBuf loc_off, l_pkt, l_time;         // the last advance's local deliveries
     DevBuf words;                  // status, n_sent, n_local, n_stored, min task time
     ScanScratch scan;
     uint32_t n_hosts = 0, first_host = 0, cap = 0;
     uint64_t n_stored = 0;         // packets queued or cached after the last advance
     uint64_t prev_end = 0;         // the last advance's window_end
+    bool advanced = false;         // an advance has run since the setup (b_* hold its batch)
     bool ready = false;
+};
+
+// The packet ledger (ledger.hip): each batch's (total size, packet id) per packet, kept on the
+// device from the relay round that sent the batch until its last event has popped.
+struct LedgerState {
+    LedgerBook book;               // the host's bookkeeping (ledger_book.h); exact between calls:
+                                   // every gather ends with a read-back of the live counts
+    DevBuf arena;                  // uint2 {size, pkt} entries, a batch = one contiguous slice
+    DevBuf rows;                   // LedgerRow per slot (batch & mask); read-only to the gather
+    DevBuf pops;                   // [slots] u32: the running gather's pops per batch, zero between calls
+    DevBuf g_size, g_pkt;          // the last gather's outputs
+    DevBuf words;                  // status, then the live count of every batch from oldest to newest
+    PinBuf pin;                    // their host copy
+    bool ready = false;
+};
+
+// The two-call scheduling window (window.cpp): what shd_window_close leaves for the next open.
+struct WindowState {
+    bool opened = false;           // an open without its close
+    uint64_t window_end = 0;       // the open's
+    bool has_out = false;          // `out` is a relay output in the event queues' lent slot, not merged yet
+    shd_relay_out out{};
+    DevBuf status;                 // the last close's per-packet SHD_PKT_* (engine-owned)
 };
 
 struct RelayState {
@@ -330,4 +355,6 @@ struct shd_ctx {
     shd::TbState tb;
     shd::InboundState inb;
     shd::OutboundState outb;
+    shd::LedgerState ledger;
+    shd::WindowState win;
 };

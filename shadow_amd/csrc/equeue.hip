@@ -1124,6 +1124,13 @@ shd_status shd_equeue_advance(shd_ctx* ctx, const shd_relay_out* d_batch, uint64
     return SHD_OK;
 }
 
+shd_status shd_equeue_next_batch(shd_ctx* ctx, uint64_t* batch) {
+    if (!ctx || !batch) return SHD_ERR_INVALID;
+    if (!ctx->eq.ready) return SHD_ERR_STATE;
+    *batch = ctx->eq.batches;
+    return SHD_OK;
+}
+
 shd_status shd_equeue_copy_popped(shd_ctx* ctx, uint32_t* off, uint64_t* deliver, uint32_t* src,
                                   uint64_t* seq, uint64_t* tag) {
     if (!ctx) return SHD_ERR_INVALID;

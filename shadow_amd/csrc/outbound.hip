@@ -47,7 +47,7 @@
 // configuration.rs:495), the loopback relay (unlimited, every packet local), the pcap and tracker
 // side effects of networkinterface_pop, and the CPU-delay model (as the inbound stage).
 //
-// Each packet leaves the stage at most once, as one record: SENT (pkt, time, dst, payload) or
+// Each packet leaves the stage at most once, as one record: SENT (pkt, time, dst, payload, size) or
 // LOCAL (pkt, time).  Host h owns a region of (its offers + queued + cached) records, bounded by a
 // scan (scan.h); the record's kind picks the end it is written at -- SENT from the front, LOCAL
 // from the back -- so the two kinds never meet and each keeps its order.  Two more scans (sent
@@ -136,7 +136,8 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
     const uint64_t* __restrict__ prio, const uint32_t* __restrict__ size, const uint32_t* __restrict__ payload,
     const uint32_t* __restrict__ dst, const uint32_t* __restrict__ pkt, OutPkt* ring_all, uint32_t cap, TbRelay* tb,
     OutRelay* rl, const uint32_t* __restrict__ reg_off, uint32_t* __restrict__ nsent, uint32_t* __restrict__ nloc,
-    uint32_t* r_pkt, uint64_t* r_time, uint32_t* r_dst, uint32_t* r_pay, uint64_t prev_end, uint64_t window_end,
+    uint32_t* r_pkt, uint64_t* r_time, uint32_t* r_dst, uint32_t* r_pay, uint32_t* r_size, uint64_t prev_end,
+    uint64_t window_end,
     uint64_t bootstrap_end, unsigned long long* words) {
     __shared__ uint64_t s_tm[kOutBatch][kOutLanes], s_pr[kOutBatch][kOutLanes];
     __shared__ uint32_t s_sz[kOutBatch][kOutLanes], s_pl[kOutBatch][kOutLanes], s_ds[kOutBatch][kOutLanes],
@@ -333,6 +334,7 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
                         r_time[w] = T;
                         r_dst[w] = d_;
                         r_pay[w] = pl_;
+                        r_size[w] = s_;   // the total size: what the destination's bucket removes (the ledger)
                         ++n_s;
                     }
                 }
@@ -386,8 +388,9 @@ __device__ __forceinline__ uint32_t outb_host_of(const uint32_t* __restrict__ o,
 __global__ __launch_bounds__(256) void outb_compact(
     uint64_t n_slots, uint32_t n_hosts, const uint32_t* __restrict__ reg_off, const uint32_t* __restrict__ src_off,
     const uint32_t* __restrict__ loc_off, const uint32_t* __restrict__ r_pkt, const uint64_t* __restrict__ r_time,
-    const uint32_t* __restrict__ r_dst, const uint32_t* __restrict__ r_pay, uint64_t* __restrict__ b_time,
-    uint32_t* __restrict__ b_dst, uint32_t* __restrict__ b_pay, uint32_t* __restrict__ b_pkt,
+    const uint32_t* __restrict__ r_dst, const uint32_t* __restrict__ r_pay, const uint32_t* __restrict__ r_size,
+    uint64_t* __restrict__ b_time, uint32_t* __restrict__ b_dst, uint32_t* __restrict__ b_pay,
+    uint32_t* __restrict__ b_pkt, uint32_t* __restrict__ b_size,
     uint32_t* __restrict__ l_pkt, uint64_t* __restrict__ l_time) {
     const uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (d < min((uint64_t)src_off[n_hosts], n_slots)) {
@@ -398,6 +401,7 @@ __global__ __launch_bounds__(256) void outb_compact(
         b_dst[d] = r_dst[i];
         b_pay[d] = r_pay[i];
         b_pkt[d] = r_pkt[i];
+        b_size[d] = r_size[i];
     }
     if (d < min((uint64_t)loc_off[n_hosts], n_slots)) {
         const uint32_t h = outb_host_of(loc_off, n_hosts, d);
@@ -449,6 +453,7 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
     O.cap = capacity;
     O.n_stored = 0;
     O.prev_end = 0;
+    O.advanced = false;
     O.ready = true;
     return SHD_OK;
 }
@@ -476,10 +481,12 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
     SHD_TRY(O.r_time.ensure(r1 * 8));
     SHD_TRY(O.r_dst.ensure(r1 * 4));
     SHD_TRY(O.r_pay.ensure(r1 * 4));
+    SHD_TRY(O.r_size.ensure(r1 * 4));
     SHD_TRY(O.b_time.ensure(r1 * 8));
     SHD_TRY(O.b_dst.ensure(r1 * 4));
     SHD_TRY(O.b_pay.ensure(r1 * 4));
     SHD_TRY(O.b_pkt.ensure(r1 * 4));
+    SHD_TRY(O.b_size.ensure(r1 * 4));
     SHD_TRY(O.l_pkt.ensure(r1 * 4));
     SHD_TRY(O.l_time.ensure(r1 * 8));
     unsigned long long* words = O.words.as<unsigned long long>();
@@ -498,8 +505,8 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
         outb_run<<<div_up(H, kOutLanes), kOutLanes, 0, s>>>(H, O.first_host, off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt,
                                                 O.ring.as<OutPkt>(), O.cap, O.tb.as<TbRelay>(), O.rl.as<OutRelay>(),
                                                 cnt, nsent, nloc, O.r_pkt.as<uint32_t>(), O.r_time.as<uint64_t>(),
-                                                O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.prev_end,
-                                                window_end, bootstrap_end, words);
+                                                O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.r_size.as<uint32_t>(),
+                                                O.prev_end, window_end, bootstrap_end, words);
         SHD_HIP(hipGetLastError());
         // the sent and the local counts per host, both in one launch -> src_off, loc_off
         SHD_TRY(scan_excl2(O.scan, nsent, O.src_off.as<uint32_t>(), nloc, O.loc_off.as<uint32_t>(), (uint64_t)H + 1, s));
@@ -507,8 +514,9 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
             // (a thread per slot: the totals are known on the device only; the surplus threads leave at once)
             outb_compact<<<div_up(n_slots, 256), 256, 0, s>>>(
                 n_slots, H, cnt, O.src_off.as<uint32_t>(), O.loc_off.as<uint32_t>(), O.r_pkt.as<uint32_t>(),
-                O.r_time.as<uint64_t>(), O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.b_time.as<uint64_t>(),
-                O.b_dst.as<uint32_t>(), O.b_pay.as<uint32_t>(), O.b_pkt.as<uint32_t>(), O.l_pkt.as<uint32_t>(),
+                O.r_time.as<uint64_t>(), O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.r_size.as<uint32_t>(),
+                O.b_time.as<uint64_t>(), O.b_dst.as<uint32_t>(), O.b_pay.as<uint32_t>(), O.b_pkt.as<uint32_t>(),
+                O.b_size.as<uint32_t>(), O.l_pkt.as<uint32_t>(),
                 O.l_time.as<uint64_t>());
             SHD_HIP(hipGetLastError());
         }
@@ -524,6 +532,7 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
     }
     O.n_stored = w[3];
     O.prev_end = window_end;
+    O.advanced = true;
     if (d_batch_out) {
         d_batch_out->n_packets = w[1];
         d_batch_out->src_off = O.src_off.as<uint32_t>();
@@ -539,6 +548,15 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
     if (n_local) *n_local = w[2];
     if (n_stored) *n_stored = w[3];
     if (next_task_time) *next_task_time = w[4];
+    return SHD_OK;
+}
+
+shd_status shd_outbound_sent_sizes(shd_ctx* ctx, const uint32_t** d_size) {
+    if (!ctx || !d_size) return SHD_ERR_INVALID;
+    OutboundState& O = ctx->outb;
+    if (!O.ready) return SHD_ERR_STATE;   // not set up, or a contract error since: as shd_outbound_get_state
+    // (before the first advance the array is empty: the batch it belongs to has no entry)
+    *d_size = O.advanced ? O.b_size.as<uint32_t>() : nullptr;
     return SHD_OK;
 }
 

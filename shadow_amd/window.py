@@ -1,0 +1,112 @@
+"""Host-side mirror of the two-call scheduling window (``shd_window_open`` / ``shd_window_close``).
+
+A window is two engine calls with the CPU in between: ``open`` merges the relay output the last
+close left into the event queues, pops the window's events, gathers their sizes and ids from the
+packet ledger and runs the inbound stage; the caller's sockets turn the inbound records into this
+window's offers; ``close`` runs the outbound stage, the relay round and the ledger record.  No
+packet data crosses the host.  The relay, the event queues, the runahead, both stages and the
+ledger are set up by the caller (``Relay``, ``EventQueues``, ``Runahead``, ``InboundStage``,
+``OutboundStage``, ``PacketLedger``) on one engine, for the same hosts; sharded engines are not
+covered.  No CPU fallback: without the native library or a gfx950 GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native as N
+from .inbound import DeviceRecords, Records
+
+IDLE = 2**64 - 1
+
+
+@dataclass
+class Opened:
+    """``shd_window_open``'s outputs: the inbound stage's records (engine-owned device arrays,
+    valid until the next open) and the queues' totals."""
+    records: DeviceRecords
+    n_popped: int
+    n_pending: int
+    queue_next_time: int   # IDLE when the queues are empty
+
+
+@dataclass
+class Closed:
+    """``shd_window_close``'s outputs: device pointers valid until the next close."""
+    sent_pkt: int
+    sent_status: int
+    loc_off: int
+    loc_pkt: int
+    loc_time: int
+    n_batch: int           # batch entries: packets the outbound stage sent
+    n_events: int          # of them SENT by the relay: events for the queues
+    n_local: int
+    n_stored: int
+    next_task_time: int    # the outbound stage's, IDLE when none
+    min_deliver: int       # the relay output's earliest deliver time, IDLE when none
+
+
+@dataclass
+class ClosedHost:
+    sent_pkt: np.ndarray     # u32 [n_batch]
+    sent_status: np.ndarray  # u8 [n_batch]: PKT_SKIPPED / PKT_DROPPED / PKT_SENT
+    loc_off: np.ndarray      # u32 [n_hosts + 1]
+    loc_pkt: np.ndarray      # u32
+    loc_time: np.ndarray     # u64
+
+
+def _as_p(a):
+    return a if a is None or isinstance(a, (int, C.c_void_p)) else N.ptr(a)
+
+
+class Window:
+    def __init__(self, engine, n_hosts: int):
+        self.eng = engine
+        self.n_hosts = int(n_hosts)
+
+    def open(self, window_end: int, bootstrap_end: int = 0) -> Opened:
+        off, pkt, time, kind = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n_out, n_stored, nxt, n_pop, n_pend, qn = (C.c_uint64(0) for _ in range(6))
+        N.check(self.eng.lib.shd_window_open(
+            self.eng.ctx, int(window_end), int(bootstrap_end), C.byref(off), C.byref(pkt), C.byref(time),
+            C.byref(kind), C.byref(n_out), C.byref(n_stored), C.byref(nxt), C.byref(n_pop), C.byref(n_pend),
+            C.byref(qn)), "shd_window_open")
+        rec = DeviceRecords(off.value, pkt.value, time.value, kind.value, n_out.value, n_stored.value, nxt.value)
+        return Opened(rec, n_pop.value, n_pend.value, qn.value)
+
+    def close(self, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers: int, window_end: int,
+              sim_end: int, bootstrap_end: int = 0) -> Closed:
+        """The offers as device pointers (ints, ctypes pointers or torch tensors; all None for none)."""
+        sp, ss, lo, lp, lt = (C.c_void_p() for _ in range(5))
+        n_batch, n_ev, n_local, n_stored, nxt, md = (C.c_uint64(0) for _ in range(6))
+        N.check(self.eng.lib.shd_window_close(
+            self.eng.ctx, _as_p(d_off), _as_p(d_time), _as_p(d_prio), _as_p(d_size), _as_p(d_payload), _as_p(d_dst),
+            _as_p(d_pkt), int(n_offers), int(window_end), int(sim_end), int(bootstrap_end), C.byref(sp), C.byref(ss),
+            C.byref(n_batch), C.byref(n_ev), C.byref(lo), C.byref(lp), C.byref(lt), C.byref(n_local),
+            C.byref(n_stored), C.byref(nxt), C.byref(md)), "shd_window_close")
+        return Closed(sp.value, ss.value, lo.value, lp.value, lt.value, n_batch.value, n_ev.value, n_local.value,
+                      n_stored.value, nxt.value, md.value)
+
+    def _copy(self, pairs):
+        for dst, src in pairs:
+            if dst.nbytes:
+                N.check(self.eng.lib.shd_copy_to_host(self.eng.ctx, N.ptr(dst), C.c_void_p(src), dst.nbytes),
+                        "shd_copy_to_host")
+
+    def records(self, o: Opened) -> Records:
+        """Host copies of an open's inbound records."""
+        r = o.records
+        off = np.zeros(self.n_hosts + 1, np.uint32)
+        pkt, time, kind = np.zeros(r.n_out, np.uint32), np.zeros(r.n_out, np.uint64), np.zeros(r.n_out, np.uint8)
+        self._copy(((off, r.off), (pkt, r.pkt), (time, r.time), (kind, r.kind)))
+        return Records(off, pkt, time, kind, r.n_stored, r.next_task_time)
+
+    def closed(self, c: Closed) -> ClosedHost:
+        """Host copies of a close's sent ids, statuses and local deliveries."""
+        sp, ss = np.zeros(c.n_batch, np.uint32), np.zeros(c.n_batch, np.uint8)
+        lo = np.zeros(self.n_hosts + 1, np.uint32)
+        lp, lt = np.zeros(c.n_local, np.uint32), np.zeros(c.n_local, np.uint64)
+        self._copy(((sp, c.sent_pkt), (ss, c.sent_status), (lo, c.loc_off), (lp, c.loc_pkt), (lt, c.loc_time)))
+        return ClosedHost(sp, ss, lo, lp, lt)

@@ -1,0 +1,181 @@
+"""Time the two-call scheduling window and the packet ledger on one C5-shaped steady state.
+
+    python tools/window_probe.py [--hosts 100000] [--per-host 100] [--windows 14] [--timed 6] [--nodes 100]
+                                 [--lat-windows 6]
+
+Every host offers about --per-host packets per 1 ms window (sizes 20% 52 B / 60% 1500 B / 20%
+uniform, times sorted per host, destinations uniform; every host at the reference's default
+1 Gbit/s both ways), generated on the device.  Path latencies are spread over 1 .. --lat-windows
+windows, so that many batches have events pending at once and every window pops events of all of
+them.  The same workload (same seeds, fresh stages) runs twice in one session:
+
+  window    shd_window_open + shd_window_close per window
+  separate  the calls the window makes, one by one, each timed: shd_equeue_advance,
+            shd_ledger_gather, shd_inbound_advance (the gathered arrays: the sizes already lie on
+            the device), shd_outbound_advance, shd_relay_round_device, shd_ledger_record
+
+Host clock around each call.  Every call but the record returns after its own pinned read-back;
+the record makes no host synchronisation, so its time is taken to the end of a stream
+synchronisation that follows it (the launch alone is printed too).  The last --timed windows
+count; the ones before fill the queues.  Prints one JSON line."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MS = 10**6
+HEADER = 52
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--hosts", type=int, default=100_000)
+    ap.add_argument("--per-host", type=int, default=100)
+    ap.add_argument("--windows", type=int, default=14)
+    ap.add_argument("--timed", type=int, default=6)
+    ap.add_argument("--nodes", type=int, default=100)
+    ap.add_argument("--lat-windows", type=int, default=6)
+    ap.add_argument("--ring", type=int, default=1024)
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from shadow_amd import _native as N
+    from shadow_amd import synth
+    from shadow_amd.equeue import EventQueues
+    from shadow_amd.inbound import InboundStage
+    from shadow_amd.ledger import PacketLedger
+    from shadow_amd.outbound import OutboundStage
+    from shadow_amd.relay import Relay
+    from shadow_amd.rounds import Runahead
+    from shadow_amd.routing import Engine
+    from shadow_amd.tbucket import SIM_START
+    from shadow_amd.window import Window
+
+    H, NN = a.hosts, a.nodes
+    rs = np.random.default_rng(11)
+    lat = rs.integers(MS, a.lat_windows * MS + 1, (NN, NN)).astype(np.uint64)
+    lat[0, 0] = MS
+    loss = np.full((NN, NN), 0.01, np.float32)
+    host_node = synth.c5_host_nodes(H, NN)
+    rng0 = synth.host_rng_states(H, 1)
+    end_time = SIM_START + 10**12
+
+    def window(g, start, w):
+        lo, hi = max(a.per_host * 4 // 5, 0), a.per_host * 6 // 5 + 1
+        cnt = torch.randint(lo, hi, (H,), generator=g, device="cuda")
+        off = torch.zeros(H + 1, dtype=torch.int64, device="cuda")
+        off[1:] = torch.cumsum(cnt, 0)
+        n = int(off[-1])
+        host = torch.repeat_interleave(torch.arange(H, device="cuda"), cnt)
+        key, _ = torch.sort(host * MS + torch.randint(0, MS, (n,), generator=g, device="cuda"))
+        t = start + (key - host * MS)
+        u = torch.rand(n, generator=g, device="cuda")
+        size = torch.where(u < 0.2, 52, torch.where(u < 0.8, 1500, torch.randint(HEADER, 1501, (n,), generator=g,
+                                                                                   device="cuda")))
+        idx = torch.arange(n, device="cuda")
+        dst = torch.randint(0, H, (n,), generator=g, device="cuda")
+        pkt = ((idx + w * 50_000_000) & 0x7FFFFFFF).int()
+        return (off.int(), t.contiguous(), (idx + (w << 32)).contiguous(), size.int(), (size - HEADER).int(), dst.int(),
+                pkt), n
+
+    def setup(eng):
+        parts = [Relay(host_node, rng0, np.zeros(H, np.uint64), lat, loss, engine=eng), EventQueues(eng, H),
+                 Runahead(eng, False, MS),
+                 OutboundStage.from_bandwidth(eng, [125_000_000] * H, SIM_START, ring_capacity=a.ring),
+                 InboundStage.from_bandwidth(eng, [125_000_000] * H, SIM_START, ring_capacity=a.ring),
+                 PacketLedger(eng)]
+        return parts
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    res = {"hosts": H, "nodes": NN, "lat_windows": a.lat_windows}
+    shape = []
+
+    with Engine(0) as eng:   # ---- the window calls
+        parts = setup(eng)
+        win, led = Window(eng, H), parts[-1]
+        g = torch.Generator(device="cuda").manual_seed(5)
+        t_open, t_close, start = [], [], SIM_START
+        for w in range(a.windows):
+            arr, n = window(g, start, w)
+            op, ms_o = clock(lambda: win.open(start + MS))
+            cl, ms_c = clock(lambda: win.close(*arr, n, start + MS, end_time))
+            t_open.append(ms_o)
+            t_close.append(ms_c)
+            s = led.stats()
+            shape.append((n, op.n_popped, op.n_pending, cl.n_batch, cl.n_events, s.live_batches, s.entries_held))
+            start += MS
+        del parts
+
+    with Engine(0) as eng:   # ---- the same calls one by one
+        relay, queues, _, ostage, istage, led = parts = setup(eng)
+        g = torch.Generator(device="cuda").manual_seed(5)
+        names = ("equeue", "gather", "inbound", "outbound", "relay", "record", "record_launch")
+        t = {k: [] for k in names}
+        out, status, start = None, None, SIM_START
+        for w in range(a.windows):
+            arr, n = window(g, start, w)
+            we = start + MS
+            eq, ms = clock(lambda: queues.advance_device(out, we))
+            t["equeue"].append(ms)
+            (d_size, d_pkt), ms = clock(lambda: led.gather_device(eq.tag, eq.n_popped))
+            t["gather"].append(ms)
+            ib, ms = clock(lambda: istage.advance_device(eq.off, eq.deliver, d_size, d_pkt, eq.n_popped, we))
+            t["inbound"].append(ms)
+            ob, ms = clock(lambda: ostage.advance_device(*arr, n, we))
+            t["outbound"].append(ms)
+            out = None
+            t_relay = t_rec = t_launch = 0.0
+            if ob.n_sent:
+                out = queues.batch_buffers(ob.n_sent)
+                if status is None or len(status) < ob.n_sent:
+                    status = torch.empty(ob.n_sent * 5 // 4, dtype=torch.uint8, device="cuda")
+                out.status = status.data_ptr()
+                rd = N.Round(we, end_time, 0)
+                _, t_relay = clock(lambda: N.check(eng.lib.shd_relay_round_device(eng.ctx, C.byref(ob.batch), C.byref(rd),
+                                                                                 C.byref(out)), "relay"))
+                sizes = C.c_void_p()
+                N.check(eng.lib.shd_outbound_sent_sizes(eng.ctx, C.byref(sizes)), "sizes")
+                number = led.next_batch()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                led.record(number, sizes.value, ob.sent_pkt, ob.n_sent, out.n_sent)
+                t_launch = (time.perf_counter() - t0) * 1e3
+                torch.cuda.synchronize()
+                t_rec = (time.perf_counter() - t0) * 1e3
+            t["relay"].append(t_relay)
+            t["record"].append(t_rec)
+            t["record_launch"].append(t_launch)
+            start += MS
+        del parts
+
+    k = a.timed
+    med = lambda x: round(statistics.median(x[-k:]), 3)  # noqa: E731
+    res["per_window_offers_popped_pending_batch_events_livebatches_entries"] = shape[-k:]
+    res["open_ms"], res["close_ms"] = med(t_open), med(t_close)
+    res["open_plus_close_ms"] = round(res["open_ms"] + res["close_ms"], 3)
+    for name in names:
+        res[name + "_ms"] = med(t[name])
+    res["four_stage_calls_ms"] = round(sum(res[x + "_ms"] for x in ("equeue", "inbound", "outbound", "relay")), 3)
+    res["separate_sum_ms"] = round(res["four_stage_calls_ms"] + res["gather_ms"] + res["record_ms"], 3)
+    res["open_ms_all"] = [round(x, 3) for x in t_open]
+    res["close_ms_all"] = [round(x, 3) for x in t_close]
+    res["gather_ms_all"] = [round(x, 3) for x in t["gather"]]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
