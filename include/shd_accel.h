@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 6
+#define SHD_ABI_VERSION 7
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -782,6 +782,38 @@ shd_status shd_ledger_setup(shd_ctx* ctx, uint32_t max_live_batches);
  * max_live_batches or more numbers above the oldest one held. */
 shd_status shd_ledger_record(shd_ctx* ctx, uint64_t batch, const uint32_t* d_size, const uint32_t* d_pkt,
                              uint64_t n_packets, uint64_t n_live);
+/* The record after a committed shd_relay_round_sharded, a collective: every rank of the
+ * communicator calls it.  A sharded round hands a rank the events of its own destination hosts,
+ * and their ev_pkt is the packet's index in its SENDER rank's batch, which the receiver does not
+ * hold.  d_size / d_pkt / d_dst_host / d_status [n_packets]: this rank's batch entries as
+ * shd_ledger_record takes them, with the batch's destinations and the round's SHD_PKT_* statuses
+ * (device arrays); d_out: this rank's shd_relay_round_sharded output.  Each SHD_PKT_SENT entry's
+ * (size, id) goes to the rank that owns its destination host (shd_shard_range).  On return this
+ * rank's ledger holds, under `batch` (ITS OWN shd_equeue_next_batch: batch numbers are per rank),
+ * one entry per event it received -- d_out->n_events of them, all live; the senders' entries in
+ * rank order, each sender's in its batch order -- and d_out->ev_pkt[e] has been rewritten in place
+ * to the index in that slice, so shd_equeue_advance and shd_ledger_gather work unchanged (tag =
+ * batch << 32 | index).  A rank that received nothing records nothing and passes no batch to its
+ * queues.  Packet ids travel unchanged: the inbound records of a rank carry ids chosen by the
+ * sender rank's caller, so a sharded caller picks ids that name a packet across the ranks.
+ * local: the caller's own status on entry (SHD_OK, or a failure it carries into the call instead
+ * of leaving its peers alone in the collective).  Everything that can differ between the ranks --
+ * local, a NULL array with n_packets > 0, a ledger or relay not set up, a batch number not above
+ * the last one recorded, a ledger that already spans max_live_batches numbers, an allocation
+ * failure -- travels with the sizes in the one small all-to-all the call starts with: if any
+ * rank's status is not SHD_OK every rank returns the lowest failing rank's status, with its ledger
+ * as it was.  Two host synchronisations: that read-back and the remap's status.  (The remap goes
+ * through an inverse table of one 4-byte slot per batch entry of every sender, allocated after
+ * the exchange; knob LEDGER_REMAP_SEARCH=1, or a table that cannot be had: a binary search of the
+ * sender's indices instead, same results.)  SHD_ERR_INVALID
+ * after the exchange, on that rank alone: an event whose ev_pkt names a packet its sender did not
+ * send has UINT32_MAX there, and every later ledger call of the rank returns SHD_ERR_STATE until
+ * shd_ledger_setup, as after a refused gather.  Without a collective: SHD_ERR_STATE without a
+ * communicator, SHD_ERR_INVALID for a NULL ctx or d_out or more than 256 ranks.  At one rank the
+ * call is shd_ledger_record with n_live = d_out->n_sent. */
+shd_status shd_ledger_record_sharded(shd_ctx* ctx, uint64_t batch, const uint32_t* d_size, const uint32_t* d_pkt,
+                                     const uint32_t* d_dst_host, const uint8_t* d_status, uint64_t n_packets,
+                                     shd_relay_out* d_out, shd_status local);
 /* d_tag[n] as shd_equeue_out.tag lies on the device -> engine-owned device arrays (*d_size)[n],
  * (*d_pkt)[n], valid until the next gather: what shd_inbound_advance takes.  Lowers each named
  * batch's live count; a batch at 0 is retired (the call ends with one read-back of the status and
@@ -823,12 +855,31 @@ shd_status shd_ledger_stats(shd_ctx* ctx, uint64_t* live_batches, uint64_t* live
  * batch entry), *n_batch (batch entries), *n_events (of them sent: events for the queues) and
  * *min_deliver (shd_relay_out.min_deliver; UINT64_MAX: none).
  * SHD_ERR_STATE, nothing changed: relay, queues, runahead, both stages and the ledger are not all
- * set up for the same host count with first_host 0, or the context is under a communicator of
- * more than one rank (sharded windows are not covered: a received event's index names the sender
- * rank's batch, which the receiver's ledger does not hold); a close without its open, two opens
- * in a row.  SHD_ERR_INVALID before anything runs: a close whose window_end is not its open's, or
+ * set up for the same host count with first_host 0; a close without its open, two opens in a
+ * row.  SHD_ERR_INVALID before anything runs: a close whose window_end is not its open's, or
  * a close while the ledger already spans max_live_batches batch numbers.  Otherwise the statuses
  * of the stages, as they return them.
+ *
+ * Under a communicator of N > 1 ranks a window runs on each rank's shard [lo, hi) of the hosts
+ * (shd_shard_range): the relay set up under the communicator, the queues holding the shard, both
+ * stages set up for hi - lo hosts, the outbound stage with first_host = lo, runahead and ledger on
+ * every rank (a rank without hosts needs neither queues nor stages); anything else stays
+ * SHD_ERR_STATE.  The open is local, no collective: queues -> gather -> inbound stage on the
+ * rank's hosts.  A rank whose open fails must not leave its peers alone in the close: agreeing
+ * after the opens is the caller's job (no rank calls the close, or every rank does).  The close
+ * is a collective with the same sequence of collectives on every rank, whatever happens locally:
+ *   1. the preconditions (the parts ready, the open seen, window_end its open's, room in the
+ *      ledger) agreed in one small collective: if any rank fails them every rank returns the
+ *      lowest failing rank's status and nothing has run anywhere.  One refusal comes without a
+ *      collective: SHD_ERR_STATE when the relay is not set up under this communicator
+ *   2. shd_outbound_advance, local; a rank where it fails still enters the round
+ *   3. shd_relay_round_sharded, always (an empty batch, a rank without hosts): an outbound
+ *      failure rides in the round's own status agreement, so the round commits on no rank and
+ *      every rank's close returns that status (the peers' outbound stages have run their window)
+ *   4. shd_ledger_record_sharded
+ * *n_events is the number of events this rank RECEIVED (what its queues merge at the next open),
+ * *n_batch and *sent_status cover its own sends, *min_deliver is the all-rank value.  Packet ids
+ * travel unchanged between the ranks (see shd_ledger_record_sharded).
  * ------------------------------------------------------------------------------------- */
 shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap_end,
                            const uint32_t** out_off, const uint32_t** out_pkt, const uint64_t** out_time,

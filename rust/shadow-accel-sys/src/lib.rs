@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 6;
+pub const SHD_ABI_VERSION: u32 = 7;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -236,6 +236,7 @@ extern "C" {
     pub fn shd_outbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, queue_len: *mut u32, head_pkt: *mut u32, bucket: *mut shd_tb_state) -> shd_status;
     pub fn shd_ledger_setup(ctx: *mut shd_ctx, max_live_batches: u32) -> shd_status;
     pub fn shd_ledger_record(ctx: *mut shd_ctx, batch: u64, d_size: *const u32, d_pkt: *const u32, n_packets: u64, n_live: u64) -> shd_status;
+    pub fn shd_ledger_record_sharded(ctx: *mut shd_ctx, batch: u64, d_size: *const u32, d_pkt: *const u32, d_dst_host: *const u32, d_status: *const u8, n_packets: u64, d_out: *mut shd_relay_out, local: shd_status) -> shd_status;
     pub fn shd_ledger_gather(ctx: *mut shd_ctx, d_tag: *const u64, n: u64, d_size: *mut *const u32, d_pkt: *mut *const u32) -> shd_status;
     pub fn shd_ledger_stats(ctx: *mut shd_ctx, live_batches: *mut u64, live_events: *mut u64, entries_held: *mut u64, oldest_batch: *mut u64) -> shd_status;
     pub fn shd_window_open(ctx: *mut shd_ctx, window_end: u64, bootstrap_end: u64, out_off: *mut *const u32, out_pkt: *mut *const u32, out_time: *mut *const u64, out_kind: *mut *const u8, n_out: *mut u64, n_stored: *mut u64, inbound_next_task: *mut u64, n_popped: *mut u64, n_pending: *mut u64, queue_next_time: *mut u64) -> shd_status;

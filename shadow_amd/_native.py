@@ -42,7 +42,7 @@ EXPORTED = [
     "shd_inbound_setup", "shd_inbound_advance", "shd_inbound_get_state",
     "shd_outbound_setup", "shd_outbound_advance", "shd_outbound_get_state", "shd_outbound_sent_sizes",
     "shd_equeue_next_batch", "shd_ledger_setup", "shd_ledger_record", "shd_ledger_gather", "shd_ledger_stats",
-    "shd_window_open", "shd_window_close",
+    "shd_window_open", "shd_window_close", "shd_ledger_record_sharded",
 ]
 COMM_ID_BYTES = 128
 
@@ -237,6 +237,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_equeue_next_batch": (I32, [P, P]),
         "shd_ledger_setup": (I32, [P, U32]),
         "shd_ledger_record": (I32, [P, U64, P, P, U64, U64]),
+        "shd_ledger_record_sharded": (I32, [P, U64, P, P, P, P, U64, P, I32]),
         "shd_ledger_gather": (I32, [P, P, U64, P, P]),
         "shd_ledger_stats": (I32, [P, P, P, P, P]),
         "shd_window_open": (I32, [P, U64, U64, P, P, P, P, P, P, P, P, P, P]),

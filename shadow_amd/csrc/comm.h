@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/shd_accel.h"
+#include "shard.h"
 
 namespace shd {
 
@@ -40,8 +41,11 @@ struct Comm {
 };
 
 // device words of shd_ctx::comm_scratch: the sharded routing build's status agreement (16 B
-// per rank + this rank's 16 B) and the sharded relay's growth agreement (8 B per rank)
-inline size_t comm_scratch_bytes(int n_ranks) { return ((size_t)n_ranks + 1) * 16 + (size_t)n_ranks * 8 + 64; }
+// per rank + this rank's 16 B) and the sharded relay's growth agreement (8 B per rank); behind
+// them the sharded ledger record's sizing words, three sent to and three received from every rank
+// (ledger.hip), which the sharded window close's one-word agreement uses as well
+inline size_t comm_ledger_words_at(int n_ranks) { return ((size_t)n_ranks + 1) * 16 + (size_t)n_ranks * 8 + 64; }
+inline size_t comm_scratch_bytes(int n_ranks) { return comm_ledger_words_at(n_ranks) + (size_t)n_ranks * 48; }
 
 // Row / host shard of rank r among n ranks: contiguous blocks of ceil(total / n).
 inline void shard_range(uint32_t total, int n, int r, uint32_t* lo, uint32_t* hi) {

@@ -178,6 +178,11 @@ struct LedgerState {
     DevBuf g_size, g_pkt;          // the last gather's outputs
     DevBuf words;                  // status, then the live count of every batch from oldest to newest
     PinBuf pin;                    // their host copy
+    // shd_ledger_record_sharded: the batch's SENT entries packed per destination rank (index in the
+    // batch, {size, pkt}), what the senders' ranks sent here, the per-(rank, workgroup) counts
+    // and their scan, the remap's status word
+    DevBuf x_sidx, x_sent, x_ridx, x_rent, x_cnt, x_st, x_inv;
+    ScanScratch x_scan;
     bool ready = false;
 };
 
@@ -188,6 +193,10 @@ struct WindowState {
     bool has_out = false;          // `out` is a relay output in the event queues' lent slot, not merged yet
     shd_relay_out out{};
     DevBuf status;                 // the last close's per-packet SHD_PKT_* (engine-owned)
+    // under a communicator of > 1 ranks `out` is the sharded round's engine-owned output (valid
+    // until the next round) and out_batch the number its events were recorded under
+    uint64_t out_batch = 0;
+    DevBuf no_off;                 // a zero: the batch offsets of a rank without hosts
 };
 
 struct RelayState {
@@ -302,6 +311,13 @@ shd_status wait_marker(shd_ctx* ctx, hipStream_t s);
 // a committed relay round's (all-rank) reductions: the runahead update (runahead.rs:60-115) and
 // the earliest deliver time of the relay output that the queues have not merged yet (rounds.cpp)
 void round_note(shd_ctx* ctx, uint64_t min_deliver, uint64_t min_latency);
+// shd_relay_round_sharded with the caller's own status on entry (relay.hip): a failure is carried
+// into the round's status agreement -- the local pipeline is skipped, the round commits nowhere
+shd_status relay_round_sharded_local(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o,
+                                     shd_status local);
+// One small collective under a communicator of > 1 ranks (ledger.hip): every rank passes its own
+// status and all return the lowest failing rank's (SHD_OK: none failed); one host synchronisation
+shd_status comm_agree(shd_ctx* ctx, shd_status local);
 // free the host mirror of the resident table (it follows the table)
 void drop_mirror(shd_ctx* ctx);
 }  // namespace shd

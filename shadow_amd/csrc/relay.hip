@@ -2900,8 +2900,10 @@ static shd_status relay_recv_grow(RelayState& R, uint64_t n) {
     return SHD_OK;
 }
 
+// local: the caller's own status on entry (a failure skips the local pipeline and is this rank's
+// status in the sizing row, so the round commits on no rank)
 static shd_status relay_round_sharded_x24(shd_ctx* ctx, const shd_batch* b, const shd_round* rd,
-                                          shd_relay_out* d_out) {
+                                          shd_relay_out* d_out, shd_status local = SHD_OK) {
     RelayState& R = ctx->relay;
     Comm& C = *ctx->comm;
     hipStream_t s = ctx->stream;
@@ -2910,10 +2912,11 @@ static shd_status relay_round_sharded_x24(shd_ctx* ctx, const shd_batch* b, cons
     const size_t nn = std::max<uint64_t>(n, 1);
     // 1. the local pipeline into internal buffers (the caller's status array); a failure here is
     //    this rank's status in the sizing row, not a return
-    shd_status st = SHD_OK;
+    shd_status st = local;
     shd_relay_out lo{};
-    if (R.ev_deliver.ensure(nn * 8) != SHD_OK || R.ev_src.ensure(nn * 4) != SHD_OK ||
-        R.ev_seq.ensure(nn * 8) != SHD_OK || R.ev_pkt.ensure(nn * 4) != SHD_OK || R.x_rec.ensure(nn * 24) != SHD_OK)
+    if (st == SHD_OK &&
+        (R.ev_deliver.ensure(nn * 8) != SHD_OK || R.ev_src.ensure(nn * 4) != SHD_OK ||
+         R.ev_seq.ensure(nn * 8) != SHD_OK || R.ev_pkt.ensure(nn * 4) != SHD_OK || R.x_rec.ensure(nn * 24) != SHD_OK))
         st = SHD_ERR_NOMEM;
     if (st == SHD_OK) {
         lo.status = d_out->status;
@@ -3039,7 +3042,7 @@ static shd_status relay_round_sharded_x24(shd_ctx* ctx, const shd_batch* b, cons
 // past 32 bits, more than 2^24 packets over all ranks -- and the caller then runs the packing
 // path (relay_round_sharded_x24), which reruns the round from the uncommitted state.
 static shd_status relay_round_sharded_v7(shd_ctx* ctx, const shd_batch* b, const shd_round* rd,
-                                         shd_relay_out* d_out, bool* fallback) {
+                                         shd_relay_out* d_out, bool* fallback, shd_status local = SHD_OK) {
     RelayState& R = ctx->relay;
     Comm& C = *ctx->comm;
     hipStream_t s = ctx->stream;
@@ -3054,11 +3057,11 @@ static shd_status relay_round_sharded_v7(shd_ctx* ctx, const shd_batch* b, const
     const bool ok7 = world <= 64 && R.n_src > 0 && R.table_narrow && !R.force_v1 && relay_v7_ok(ctx, n, n_bins);
     // absolute ids must fit the records' 32 bits; relative ids (a sharded flush) always do
     const bool abs_seq = R.rel_ids || R.seq_bound + n < (1ull << 32);
-    shd_status st = SHD_OK;
+    shd_status st = local;   // (the caller's own failure: as one of the local pipeline)
     shd_relay_out lo{};
     lo.status = d_out->status;
     bool ran = false;
-    if (ok7 && abs_seq) {
+    if (st == SHD_OK && ok7 && abs_seq) {
         const uint64_t nn = (uint64_t)R.n_nodes * R.n_nodes;   // the round's counter increments start at 0
         if (R.red.ensure(64) != SHD_OK || (R.count_on && R.counts_round.ensure(nn * 8) != SHD_OK))
             st = SHD_ERR_NOMEM;
@@ -3211,14 +3214,20 @@ static shd_status relay_round_sharded_v7(shd_ctx* ctx, const shd_batch* b, const
     return SHD_OK;
 }
 
-static shd_status relay_round_sharded(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* d_out) {
+static shd_status relay_round_sharded(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* d_out,
+                                      shd_status local = SHD_OK) {
     // (more hosts than the records' source bits: every rank has the same host count, so every
     // rank takes the packing path without asking; xs_sizing's registers also assume it)
     if (ctx->knobs.on(K_RELAY_SHARD_X24) || ctx->relay.n_hosts > kV7MaxHosts)
-        return relay_round_sharded_x24(ctx, b, rd, d_out);
+        return relay_round_sharded_x24(ctx, b, rd, d_out, local);
     bool fallback = false;
-    SHD_TRY(relay_round_sharded_v7(ctx, b, rd, d_out, &fallback));
-    return fallback ? relay_round_sharded_x24(ctx, b, rd, d_out) : SHD_OK;
+    SHD_TRY(relay_round_sharded_v7(ctx, b, rd, d_out, &fallback, local));
+    return fallback ? relay_round_sharded_x24(ctx, b, rd, d_out, local) : SHD_OK;
+}
+
+shd_status relay_round_sharded_local(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o,
+                                     shd_status local) {
+    return relay_round_sharded(ctx, b, rd, o, local);
 }
 
 // shd_relay_flush under a communicator (flush.hip): this rank's grouped sends, the CPU's draws

@@ -3,22 +3,117 @@
 //                      gather on the popped tags -> inbound stage
 //   [the CPU: the inbound records make the sockets answer -- this window's offers]
 //   shd_window_close   outbound stage -> relay round into the queues' lent slot -> ledger record
+// Under a communicator of more than one rank the window runs on the rank's shard of the hosts: the
+// open is local as before, the close a collective -- the sharded round, then the sharded record,
+// which brings each sent packet's (size, id) to the rank that owns its destination.
 // The stages are the ones the separate calls drive (equeue.hip, ledger.hip, inbound.hip,
 // outbound.hip, relay.hip); this file only chains them and keeps what lies between two calls.
 #include "ctx.h"
 
 using namespace shd;
 
-// relay, queues, runahead, both stages and the ledger set up for the same hosts, first_host 0, no
-// communicator of more than one rank (a received event's index would name the sender rank's batch)
+// true under a communicator of more than one rank: the window runs on the rank's shard of the hosts
+static bool window_sharded(const shd_ctx* ctx) { return ctx->comm && ctx->comm->size > 1; }
+
+// One context: relay, queues, runahead, both stages and the ledger set up for the same hosts,
+// first_host 0.  Under N > 1 ranks: the relay sharded, and for the rank's hosts [lo, hi) the queues
+// its shard, both stages hi - lo hosts, the outbound stage's first_host lo; a rank without hosts
+// needs neither queues nor stages.
 static bool window_ready(const shd_ctx* ctx) {
-    if (ctx->comm && ctx->comm->size > 1) return false;
-    if (!ctx->relay.ready || ctx->relay.sharded || !ctx->eq.ready || !ctx->rnd.ready || !ctx->inb.ready ||
-        !ctx->outb.ready || !ctx->ledger.ready)
-        return false;
+    if (!ctx->relay.ready || !ctx->rnd.ready || !ctx->ledger.ready) return false;
     const uint32_t H = ctx->relay.n_hosts;
-    return ctx->eq.n_hosts == H && ctx->eq.n_total == H && ctx->inb.n_hosts == H && ctx->outb.n_hosts == H &&
-           ctx->outb.first_host == 0;
+    uint32_t lo = 0, hi = H;
+    if (window_sharded(ctx)) {
+        if (!ctx->relay.sharded) return false;
+        shard_range(H, ctx->comm->size, ctx->comm->rank, &lo, &hi);
+        if (hi == lo) return true;
+    } else if (ctx->relay.sharded) {
+        return false;
+    }
+    if (!ctx->eq.ready || !ctx->inb.ready || !ctx->outb.ready) return false;
+    return ctx->eq.n_hosts == hi - lo && ctx->eq.host_lo == lo && ctx->eq.n_total == H && ctx->inb.n_hosts == hi - lo &&
+           ctx->outb.n_hosts == hi - lo && ctx->outb.first_host == lo;
+}
+
+static uint32_t window_own_hosts(const shd_ctx* ctx) {
+    uint32_t lo = 0, hi = ctx->relay.n_hosts;
+    if (window_sharded(ctx)) shard_range(ctx->relay.n_hosts, ctx->comm->size, ctx->comm->rank, &lo, &hi);
+    return hi - lo;
+}
+
+// a device zero: the batch offsets and the record offsets of a rank without hosts
+static shd_status window_no_off(shd_ctx* ctx) {
+    WindowState& W = ctx->win;
+    if (W.no_off.p) return SHD_OK;
+    SHD_TRY(W.no_off.ensure(16));
+    SHD_HIP(hipMemsetAsync(W.no_off.p, 0, 16, ctx->stream));
+    return SHD_OK;
+}
+
+// The close under N > 1 ranks: a collective with the same sequence of collectives on every rank,
+// whatever happens locally -- the precondition agreement, the sharded round (its own status
+// agreement carries an outbound failure: the round then commits nowhere), the sharded record.
+static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                       const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
+                                       const uint32_t* d_dst, const uint32_t* d_pkt, uint64_t n_offers,
+                                       uint64_t window_end, uint64_t sim_end, uint64_t bootstrap_end,
+                                       const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
+                                       uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                       const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                       uint64_t* outbound_next_task, uint64_t* min_deliver) {
+    WindowState& W = ctx->win;
+    SHD_HIP(hipSetDevice(ctx->device));
+    const uint32_t n_own = window_own_hosts(ctx);
+    // 1. the preconditions, agreed: after this either every rank runs the window or none has
+    shd_status pre = SHD_OK;
+    const LedgerBook& B = ctx->ledger.book;
+    if (!window_ready(ctx) || !W.opened) pre = SHD_ERR_STATE;
+    else if (window_end != W.window_end) pre = SHD_ERR_INVALID;
+    else if (n_own && B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) pre = SHD_ERR_INVALID;
+    else if (!n_own) pre = window_no_off(ctx);
+    SHD_TRY(comm_agree(ctx, pre));
+    W.opened = false;
+    W.has_out = false;
+    // 2. the outbound stage, local; a rank where it fails still enters the round
+    shd_batch batch{};
+    const uint32_t *b_pkt = nullptr, *b_size = nullptr;
+    shd_status st = SHD_OK;
+    if (n_own) {
+        st = shd_outbound_advance(ctx, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
+                                  bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local, n_stored,
+                                  outbound_next_task);
+        if (st == SHD_OK && batch.n_packets) st = shd_outbound_sent_sizes(ctx, &b_size);
+        if (st == SHD_OK && batch.n_packets) st = W.status.ensure(batch.n_packets);
+    } else {
+        batch.src_off = W.no_off.as<uint32_t>();
+        if (loc_off) *loc_off = W.no_off.as<uint32_t>();
+        if (loc_pkt) *loc_pkt = nullptr;
+        if (loc_time) *loc_time = nullptr;
+        if (n_local) *n_local = 0;
+        if (n_stored) *n_stored = 0;
+        if (outbound_next_task) *outbound_next_task = ~0ull;
+    }
+    if (st != SHD_OK) batch = shd_batch{};   // (nothing of it is read: the round skips its local pipeline)
+    // 3. the round, always: an empty batch and a rank without hosts included
+    shd_relay_out out{};
+    out.status = batch.n_packets ? W.status.as<uint8_t>() : nullptr;
+    const shd_round round{window_end, sim_end, bootstrap_end};
+    const shd_status st_round = relay_round_sharded_local(ctx, &batch, &round, &out, st);
+    // 4. the record, always: a failed round is every rank's status on entry, so every rank skips alike
+    uint64_t number = n_own ? ctx->eq.batches : 0;
+    SHD_TRY(shd_ledger_record_sharded(ctx, number, b_size, b_pkt, batch.dst_host, W.status.as<uint8_t>(),
+                                      batch.n_packets, &out, st_round));
+    W.out = out;
+    W.out_batch = number;
+    W.has_out = out.n_events > 0;
+    // a rank that received nothing passes no batch to its queues: no relay output is pending for them
+    if (n_own && !W.has_out) ctx->rnd.batch_min_deliver = ~0ull;
+    if (sent_pkt) *sent_pkt = b_pkt;
+    if (sent_status) *sent_status = W.status.as<uint8_t>();
+    if (n_batch) *n_batch = batch.n_packets;
+    if (n_events) *n_events = out.n_events;
+    if (min_deliver) *min_deliver = out.min_deliver;
+    return SHD_OK;
 }
 
 extern "C" {
@@ -30,8 +125,30 @@ shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap
     if (!ctx) return SHD_ERR_INVALID;
     WindowState& W = ctx->win;
     if (!window_ready(ctx) || W.opened) return SHD_ERR_STATE;
-    // (queues set up again since the close: the slot, and the batch in it, are gone)
-    if (W.has_out && (ctx->eq.lend < 0 || W.out.ev_deliver != ctx->eq.run[ctx->eq.lend].deliver.p)) W.has_out = false;
+    if (window_sharded(ctx)) {
+        if (window_own_hosts(ctx) == 0) {   // a rank without hosts: nothing pops, nothing is delivered
+            SHD_HIP(hipSetDevice(ctx->device));
+            SHD_TRY(window_no_off(ctx));
+            if (out_off) *out_off = W.no_off.as<uint32_t>();
+            if (out_pkt) *out_pkt = nullptr;
+            if (out_time) *out_time = nullptr;
+            if (out_kind) *out_kind = nullptr;
+            if (n_out) *n_out = 0;
+            if (n_stored) *n_stored = 0;
+            if (inbound_next_task) *inbound_next_task = ~0ull;
+            if (n_popped) *n_popped = 0;
+            if (n_pending) *n_pending = 0;
+            if (queue_next_time) *queue_next_time = ~0ull;
+            W.has_out = false;
+            W.opened = true;
+            W.window_end = window_end;
+            return SHD_OK;
+        }
+        // (relay or queues set up again since the close: the round's output, or its number, is gone)
+        if (W.has_out && (W.out.ev_deliver != ctx->relay.m_deliver.p || ctx->eq.batches != W.out_batch)) W.has_out = false;
+    } else if (W.has_out && (ctx->eq.lend < 0 || W.out.ev_deliver != ctx->eq.run[ctx->eq.lend].deliver.p)) {
+        W.has_out = false;   // (queues set up again since the close: the slot, and the batch in it, are gone)
+    }
     shd_equeue_out eo{};
     SHD_TRY(shd_equeue_advance(ctx, W.has_out ? &W.out : nullptr, window_end, &eo));
     W.has_out = false;
@@ -56,6 +173,14 @@ shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t*
                             uint64_t* outbound_next_task, uint64_t* min_deliver) {
     if (!ctx) return SHD_ERR_INVALID;
     WindowState& W = ctx->win;
+    if (window_sharded(ctx)) {
+        // the one refusal without a collective: a relay not set up under this communicator (every
+        // rank sets it up, or none); everything else is agreed between the ranks first
+        if (!ctx->relay.ready || !ctx->relay.sharded) return SHD_ERR_STATE;
+        return window_close_sharded(ctx, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
+                                    sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off, loc_pkt,
+                                    loc_time, n_local, n_stored, outbound_next_task, min_deliver);
+    }
     if (!window_ready(ctx) || !W.opened) return SHD_ERR_STATE;
     if (window_end != W.window_end) return SHD_ERR_INVALID;
     // the batch this close may send must find a row: refused here, before any stage has run

@@ -5,7 +5,8 @@ event has popped from the destination event queues.
 A popped event carries only its tag, ``(batch number << 32) | index in that batch``;
 ``shd_inbound_advance`` wants the packet's total size and the caller's packet id.
 ``PacketLedger(engine, max_live_batches)``; ``record(batch, d_size, d_pkt, n_packets, n_live)``
-keeps a batch's two device arrays; ``gather_device(d_tag, n)`` turns a window's popped tags into
+keeps a batch's two device arrays (``record_sharded`` under a communicator of several ranks: each
+sent packet's entry goes to the rank that owns its destination); ``gather_device(d_tag, n)`` turns a window's popped tags into
 the two device arrays the inbound stage takes (``gather`` is the host-array form, for tests);
 ``stats()``.  No CPU fallback: without the native library or a gfx950 GPU every call raises.
 """
@@ -49,6 +50,18 @@ class PacketLedger:
         """Device pointers (ints, ctypes pointers or torch tensors)."""
         N.check(self.eng.lib.shd_ledger_record(self.eng.ctx, int(batch), _as_p(d_size), _as_p(d_pkt), int(n_packets),
                                                int(n_live)), "shd_ledger_record")
+
+    def record_sharded(self, batch: int, d_size, d_pkt, d_dst_host, d_status, n_packets: int, relay_out,
+                       local: int = N.SHD_OK) -> None:
+        """``shd_ledger_record_sharded``, a collective: every rank of the engine's communicator
+        calls it after a committed sharded round.  This rank's batch entries with their
+        destinations and statuses (device pointers) and its ``shd_relay_round_sharded`` output
+        (``_native.RelayOut``): its ``ev_pkt`` is rewritten on the device to the index in the batch
+        recorded here under ``batch`` (this rank's own ``next_batch()``).  ``local``: a failure of
+        the caller's own to carry into the call; every rank then raises with that status."""
+        N.check(self.eng.lib.shd_ledger_record_sharded(
+            self.eng.ctx, int(batch), _as_p(d_size), _as_p(d_pkt), _as_p(d_dst_host), _as_p(d_status),
+            int(n_packets), C.byref(relay_out), int(local)), "shd_ledger_record_sharded")
 
     def gather_device(self, d_tag, n: int):
         """-> (d_size, d_pkt): engine-owned device pointers, valid until the next gather."""

@@ -6,8 +6,17 @@ packet ledger and runs the inbound stage; the caller's sockets turn the inbound 
 window's offers; ``close`` runs the outbound stage, the relay round and the ledger record.  No
 packet data crosses the host.  The relay, the event queues, the runahead, both stages and the
 ledger are set up by the caller (``Relay``, ``EventQueues``, ``Runahead``, ``InboundStage``,
-``OutboundStage``, ``PacketLedger``) on one engine, for the same hosts; sharded engines are not
-covered.  No CPU fallback: without the native library or a gfx950 GPU every call raises.
+``OutboundStage``, ``PacketLedger``) on one engine, for the same hosts.
+
+Under an engine communicator of several ranks (``shadow_amd.dist``) each rank runs the window on its
+shard ``[lo, hi)`` of the hosts: ``ShardedRelay``, ``EventQueues`` over all hosts (they keep the
+shard), both stages for ``hi - lo`` hosts, the outbound stage with ``first_host=lo``, and
+``Window(engine, hi - lo)``.  ``open`` stays local; ``close`` is a collective every rank calls: a
+failure on one rank (a wrong ``window_end``, an outbound contract violation) is raised on every
+rank.  ``Closed.n_events`` then counts the events this rank received, ``min_deliver`` is the
+all-rank value, and packet ids travel unchanged between the ranks, so the caller picks ids that
+name a packet across ranks.  No CPU fallback: without the native library or a gfx950 GPU every
+call raises.
 """
 from __future__ import annotations
 
@@ -63,6 +72,7 @@ def _as_p(a):
 
 class Window:
     def __init__(self, engine, n_hosts: int):
+        """``n_hosts``: the hosts this engine runs -- all of them, or the rank's ``hi - lo``."""
         self.eng = engine
         self.n_hosts = int(n_hosts)
 

@@ -17,7 +17,18 @@ them.  The same workload (same seeds, fresh stages) runs twice in one session:
 Host clock around each call.  Every call but the record returns after its own pinned read-back;
 the record makes no host synchronisation, so its time is taken to the end of a stream
 synchronisation that follows it (the launch alone is printed too).  The last --timed windows
-count; the ones before fill the queues.  Prints one JSON line."""
+count; the ones before fill the queues.  Prints one JSON line.
+
+    python tools/window_probe.py --ranks N [the same options]
+
+The same workload over N in-process ranks on one GPU (shd_comm_init_local, one host thread per
+rank, each rank offering its shard's packets): the sharded open and close per window, then the
+close's calls one by one -- shd_outbound_advance, shd_relay_round_sharded,
+shd_ledger_record_sharded -- with the ranks entering each timed call together.  Per call the
+median over the timed windows of the slowest rank's host clock.  The kernels of the sharded record
+(ledger_pack_count, ledger_pack_scatter, the scan, ledger_remap, ledger_record_ent) are read from
+a kernel trace of this run; the rest of the call is its sizing all-to-all with its read-back and
+the exchange.  --remap-search: the record's remap by binary search instead of its inverse table."""
 from __future__ import annotations
 
 import argparse
@@ -44,7 +55,11 @@ def main():
     ap.add_argument("--nodes", type=int, default=100)
     ap.add_argument("--lat-windows", type=int, default=6)
     ap.add_argument("--ring", type=int, default=1024)
+    ap.add_argument("--ranks", type=int, default=1)
+    ap.add_argument("--remap-search", action="store_true", help="--ranks: knob LEDGER_REMAP_SEARCH=1")
     a = ap.parse_args()
+    if a.ranks > 1:
+        return sharded(a)
 
     import numpy as np
     import torch
@@ -174,6 +189,171 @@ def main():
     res["open_ms_all"] = [round(x, 3) for x in t_open]
     res["close_ms_all"] = [round(x, 3) for x in t_close]
     res["gather_ms_all"] = [round(x, 3) for x in t["gather"]]
+    print(json.dumps(res))
+
+
+def sharded(a):
+    import threading
+
+    import numpy as np
+    import torch
+    from shadow_amd import _native as N
+    from shadow_amd import dist as D
+    from shadow_amd import synth
+    from shadow_amd.equeue import EventQueues
+    from shadow_amd.inbound import InboundStage
+    from shadow_amd.ledger import PacketLedger
+    from shadow_amd.outbound import OutboundStage
+    from shadow_amd.rounds import Runahead
+    from shadow_amd.routing import Engine
+    from shadow_amd.tbucket import SIM_START
+    from shadow_amd.window import Window
+
+    H, NN, W = a.hosts, a.nodes, a.ranks
+    rs = np.random.default_rng(11)
+    lat = rs.integers(MS, a.lat_windows * MS + 1, (NN, NN)).astype(np.uint64)
+    lat[0, 0] = MS
+    loss = np.full((NN, NN), 0.01, np.float32)
+    host_node = synth.c5_host_nodes(H, NN)
+    rng0 = synth.host_rng_states(H, 1)
+    end_time = SIM_START + 10**12
+
+    def window(g, start, w, lo, hi):
+        """The offers of hosts [lo, hi) (destinations over all hosts; ids distinct across ranks)."""
+        n_own = hi - lo
+        c_lo, c_hi = max(a.per_host * 4 // 5, 0), a.per_host * 6 // 5 + 1
+        cnt = torch.randint(c_lo, c_hi, (n_own,), generator=g, device="cuda")
+        off = torch.zeros(n_own + 1, dtype=torch.int64, device="cuda")
+        off[1:] = torch.cumsum(cnt, 0)
+        n = int(off[-1])
+        host = torch.repeat_interleave(torch.arange(n_own, device="cuda"), cnt)
+        key, _ = torch.sort(host * MS + torch.randint(0, MS, (n,), generator=g, device="cuda"))
+        t = start + (key - host * MS)
+        u = torch.rand(n, generator=g, device="cuda")
+        size = torch.where(u < 0.2, 52, torch.where(u < 0.8, 1500, torch.randint(HEADER, 1501, (n,), generator=g,
+                                                                                   device="cuda")))
+        idx = torch.arange(n, device="cuda")
+        dst = torch.randint(0, H, (n,), generator=g, device="cuda")
+        pkt = ((idx + lo * 2 * a.per_host + w * 50_000_000) & 0x7FFFFFFF).int()
+        return (off.int(), t.contiguous(), (idx + (w << 32)).contiguous(), size.int(), (size - HEADER).int(), dst.int(),
+                pkt), n
+
+    def setup(eng):
+        if a.remap_search:
+            eng.set_knob("LEDGER_REMAP_SEARCH", 1)
+        relay = D.ShardedRelay(eng, host_node, rng0, np.zeros(H, np.uint64), lat, loss)
+        n_own = relay.hi - relay.lo
+        return dict(relay=relay, queues=EventQueues(eng, H), ra=Runahead(eng, False, MS),
+                    ostage=OutboundStage.from_bandwidth(eng, [125_000_000] * n_own, SIM_START, first_host=relay.lo,
+                                                        ring_capacity=a.ring),
+                    istage=InboundStage.from_bandwidth(eng, [125_000_000] * n_own, SIM_START, ring_capacity=a.ring),
+                    ledger=PacketLedger(eng), win=Window(eng, n_own))
+
+    gate = threading.Barrier(W)
+
+    def clock(fn):
+        """The ranks enter the call together; each rank's own host clock around it."""
+        torch.cuda.synchronize()
+        gate.wait()
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    def run(fns):
+        res, errs = [None] * W, []
+
+        def wrap(i):
+            try:
+                res[i] = fns[i]()
+            except BaseException as e:   # noqa: BLE001 -- reported below
+                errs.append(e)
+                gate.abort()
+        ts = [threading.Thread(target=wrap, args=(i,)) for i in range(W)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        if errs:
+            raise errs[0]
+        return res
+
+    def engines_of():
+        engines = [Engine(0) for _ in range(W)]
+        D.comm_init_local(engines)
+        return engines
+
+    def rank_windows(p, rank):
+        g = torch.Generator(device="cuda").manual_seed(5 + rank)
+        t_open, t_close, shape, start = [], [], [], SIM_START
+        lo, hi = p["relay"].lo, p["relay"].hi
+        for w in range(a.windows):
+            arr, n = window(g, start, w, lo, hi)
+            op, ms_o = clock(lambda: p["win"].open(start + MS))
+            cl, ms_c = clock(lambda: p["win"].close(*arr, n, start + MS, end_time))
+            t_open.append(ms_o)
+            t_close.append(ms_c)
+            s = p["ledger"].stats()
+            shape.append((n, op.n_popped, op.n_pending, cl.n_batch, cl.n_events, s.live_batches, s.entries_held))
+            start += MS
+        return t_open, t_close, shape
+
+    def rank_calls(p, rank):
+        g = torch.Generator(device="cuda").manual_seed(5 + rank)
+        t = {k: [] for k in ("outbound", "relay_sharded", "record_sharded")}
+        eng, lo, hi, status, out, start = p["relay"].eng, p["relay"].lo, p["relay"].hi, None, None, SIM_START
+        for w in range(a.windows):
+            arr, n = window(g, start, w, lo, hi)
+            we = start + MS
+            eq = p["queues"].advance_device(out, we)
+            d_size, d_pkt = p["ledger"].gather_device(eq.tag, eq.n_popped)
+            p["istage"].advance_device(eq.off, eq.deliver, d_size, d_pkt, eq.n_popped, we)
+            ob, ms = clock(lambda: p["ostage"].advance_device(*arr, n, we))
+            t["outbound"].append(ms)
+            if status is None or len(status) < max(ob.n_sent, 1):
+                status = torch.empty(max(ob.n_sent, 1) * 5 // 4, dtype=torch.uint8, device="cuda")
+            out = N.RelayOut(status.data_ptr(), None, None, None, None, None, 0, 0, 0, 0, 0)
+            rd = N.Round(we, end_time, 0)
+            _, ms = clock(lambda: N.check(eng.lib.shd_relay_round_sharded(eng.ctx, C.byref(ob.batch), C.byref(rd),
+                                                                          C.byref(out)), "relay"))
+            t["relay_sharded"].append(ms)
+            sizes = C.c_void_p()
+            N.check(eng.lib.shd_outbound_sent_sizes(eng.ctx, C.byref(sizes)), "sizes")
+            number = p["ledger"].next_batch()
+            _, ms = clock(lambda: p["ledger"].record_sharded(number, sizes.value, ob.sent_pkt, ob.batch.dst_host,
+                                                             status, ob.n_sent, out))
+            t["record_sharded"].append(ms)
+            if not out.n_events:
+                out = None
+            start += MS
+        return t
+
+    k = a.timed
+    worst = lambda rows: round(statistics.median([max(x) for x in zip(*rows)][-k:]), 3)  # noqa: E731
+    res = {"hosts": H, "nodes": NN, "lat_windows": a.lat_windows, "ranks": W, "remap_search": a.remap_search}
+    engines = engines_of()
+    try:
+        parts = [setup(e) for e in engines]
+        out = run([lambda i=i: rank_windows(parts[i], i) for i in range(W)])
+        res["open_ms"] = worst([o[0] for o in out])
+        res["close_ms"] = worst([o[1] for o in out])
+        res["rank0_per_window_offers_popped_pending_batch_events_livebatches_entries"] = out[0][2][-k:]
+        res["open_ms_all_rank0"] = [round(x, 3) for x in out[0][0]]
+        res["close_ms_all_rank0"] = [round(x, 3) for x in out[0][1]]
+        del parts
+    finally:
+        for e in engines:
+            e.close()
+    engines = engines_of()
+    try:
+        parts = [setup(e) for e in engines]
+        out = run([lambda i=i: rank_calls(parts[i], i) for i in range(W)])
+        for name in ("outbound", "relay_sharded", "record_sharded"):
+            res[name + "_ms"] = worst([o[name] for o in out])
+            res[name + "_ms_all_rank0"] = [round(x, 3) for x in out[0][name]]
+        del parts
+    finally:
+        for e in engines:
+            e.close()
     print(json.dumps(res))
 
 
