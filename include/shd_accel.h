@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 7
+#define SHD_ABI_VERSION 8
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -693,28 +693,64 @@ shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_tim
  *                       Worker::send_packet (router/mod.rs:49-55), and the loop goes on
  * A task at T >= window_end stays outstanding for a later call.  The cached packet is never
  * overtaken, not by a local packet and not by a lower priority (head-of-line blocking).
- * Exactness: the merge is exact whenever a host's offers at one instant arrive in increasing
- * priority -- everything but a same-instant retransmission -- and also when the bucket does not
- * block at that instant.  Not covered: the round-robin discipline (network_interface.c:235-273;
- * FIFO is the default, configuration.rs:495), the loopback relay (unlimited, every packet local),
- * the pcap and tracker side effects of networkinterface_pop, and the CPU-delay model
- * (host.rs:708-735), as the inbound stage.
+ * Exactness (FIFO): the merge is exact whenever a host's offers at one instant arrive in
+ * increasing priority -- everything but a same-instant retransmission -- and also when the bucket
+ * does not block at that instant.
+ *
+ * The queuing discipline is interface_qdisc (configuration.rs:396-397, :930-933), chosen at the
+ * setup.  Under SHD_QDISC_ROUND_ROBIN (network_interface.c:235-273, :366-392;
+ * network_queuing_disciplines.c:29-88) the host keeps the rrQueue instead: an ordered list of
+ * distinct sockets, each with the packets it has offered in offer order (socket.c:434-467), a
+ * socket in the list exactly while it has a packet queued.  An offer appends the packet to its
+ * socket's and, if the socket is not in the rrQueue, pushes the socket at the tail
+ * (networkinterface_wantsSend: find, else push).  A pop takes the head socket's first packet; the
+ * socket goes back to the tail if it has more, else it leaves -- at the pop, before the relay
+ * knows whether the bucket blocks, so while a packet sits in the relay's cache its socket has
+ * already rotated.  Everything around the pop (notify, the merge, the cached packet, local
+ * packets, bootstrapping, the bucket, the records) is the same code for both disciplines.
+ * Exactness (round-robin): the merge is exact whenever a host's offers at one instant belong to
+ * one event (one accumulation under relay/mod.rs:124-126) or to one socket.  Two events on one
+ * host at the same nanosecond that offer on different sockets are rotated together here; in the
+ * reference the first event's task may already have drained its packets.  Within a socket packets
+ * leave in offer order: the socket's separate control buffer (socket.c:467, control packets
+ * first) is not modelled.
+ *
+ * Not covered: the loopback relay (unlimited, every packet local), the pcap and tracker side
+ * effects of networkinterface_pop, and the CPU-delay model (host.rs:708-735), as the inbound
+ * stage.
  * ------------------------------------------------------------------------------------- */
+
+/* QDiscMode (configuration.rs:396-397) */
+#define SHD_QDISC_FIFO 0
+#define SHD_QDISC_ROUND_ROBIN 1
 
 /* (Re)create n_hosts empty queues of up to `capacity` packets each, Idle relays and full
  * buckets; host h's global id (what a packet's dst is compared with) is first_host + h.  The tb_*
- * host arrays follow shd_tb_setup's rules (all three parameters 0: no bucket). */
+ * host arrays follow shd_tb_setup's rules (all three parameters 0: no bucket).  The discipline
+ * is FIFO. */
 shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
                               const uint64_t* tb_capacity, const uint64_t* tb_refill_increment,
                               const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill);
+/* shd_outbound_setup with the discipline named.  qdisc = SHD_QDISC_FIFO: shd_outbound_setup,
+ * max_sockets is ignored.  qdisc = SHD_QDISC_ROUND_ROBIN: `capacity` is still the packets a host
+ * may have queued, max_sockets the sockets it may have in its rrQueue at once.  SHD_ERR_INVALID:
+ * any other qdisc, or max_sockets == 0 under round-robin (the stage stays as it was). */
+shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
+                                    uint32_t qdisc, uint32_t max_sockets, const uint64_t* tb_capacity,
+                                    const uint64_t* tb_refill_increment, const uint64_t* tb_refill_interval_ns,
+                                    const uint64_t* tb_last_refill);
 /*
  * Advance every host over the window ending at window_end.  Device inputs: host h's offers are
- * [d_off[h], d_off[h+1]) of d_time / d_prio (FifoPacketPriority) / d_size (total packet size: what
- * the bucket removes) / d_payload (packet_getPayloadSize, passed through to shd_batch.payload) /
+ * [d_off[h], d_off[h+1]) of d_time / d_prio (the 64-bit key of the discipline: under FIFO the
+ * FifoPacketPriority; under round-robin the offering socket's canonical handle,
+ * compatsocket_getCanonicalHandle, compared for equality only, so any value is allowed -- the
+ * reference's round-robin never reads a priority and its FIFO never needs the socket) / d_size
+ * (total packet size: what the bucket removes) / d_payload (packet_getPayloadSize, passed through to shd_batch.payload) /
  * d_dst (destination HostId) / d_pkt (the caller's packet id, not UINT32_MAX); every pointer may
  * be NULL when n_offers is 0.  Input contract, per host: times non-decreasing, every time
- * < window_end and >= the previous call's window_end; priorities unique among the packets queued
- * on the host; for a host with a bucket every non-local size <= the bucket's capacity.
+ * < window_end and >= the previous call's window_end; under FIFO priorities unique among the
+ * packets queued on the host (round-robin has no priority check); under round-robin at most
+ * `capacity` packets and max_sockets sockets queued on a host; for a host with a bucket every non-local size <= the bucket's capacity.
  * Outputs, engine-owned device arrays valid until the next advance:
  *   *d_batch_out   src_off[n_hosts+1], send_time / dst_host / payload of the packets sent, grouped
  *                  by host in send order, n_packets, chance = NULL: it can be passed to
@@ -728,7 +764,7 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
  * the inbound stage's.  Any output pointer may be NULL.  No collective.
  * SHD_ERR_INVALID: the input contract is violated (an offer's time is checked before it is
  * weighed against the task), d_off is not a CSR over n_offers offers, a priority equals one still
- * queued on that host, or a queue exceeded its capacity -- every such input is refused by a check
+ * queued on that host (FIFO), or a queue exceeded its capacity or its max_sockets -- every such input is refused by a check
  * in the kernel, the window has partly run, and every later call returns SHD_ERR_STATE until
  * shd_outbound_setup; also where the reference panics (a time before a bucket's last refill).  A
  * NULL array with n_offers > 0 or a window_end below the previous one is SHD_ERR_INVALID before
@@ -747,13 +783,21 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
  * shd_outbound_get_state returns it. */
 shd_status shd_outbound_sent_sizes(shd_ctx* ctx, const uint32_t** d_size);
 /* One host's state (any pointer may be NULL): *task_time UINT64_MAX = Idle; the cached packet;
- * the queue's length and the packet at its head (the lowest priority; UINT32_MAX: empty); the
+ * the packets queued and the one the next pop takes (FIFO: the lowest priority; round-robin: the
+ * head socket's first; UINT32_MAX: empty); the
  * bucket in the struct of shd_tb_get_state (pending_until = the task time, 0 when Idle).
  * SHD_ERR_STATE while the stage is not ready -- before shd_outbound_setup, or after a contract
  * error until the next setup, as the advance; SHD_ERR_INVALID: host >= n_hosts. */
 shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_time, uint32_t* has_cached,
                                   uint32_t* cached_pkt, uint32_t* cached_size, uint32_t* queue_len,
                                   uint32_t* head_pkt, shd_tb_state* bucket);
+/* One host's rrQueue in order: handles[i] / counts[i] = the i-th socket's canonical handle and
+ * its queued packets, at most `cap` entries written (host arrays; NULL with cap = 0);
+ * *n_sockets = the sockets queued.  The cached packet's socket is listed only if it has further
+ * packets.  SHD_ERR_STATE under FIFO, and wherever shd_outbound_get_state returns it;
+ * SHD_ERR_INVALID: host >= n_hosts. */
+shd_status shd_outbound_get_sockets(shd_ctx* ctx, uint32_t host, uint64_t* handles, uint32_t* counts, uint32_t cap,
+                                    uint32_t* n_sockets);
 
 /* ---------------------------------------------------------------------------------------
  * Packet ledger: what joins the event queues to the inbound stage on the device.  A popped event

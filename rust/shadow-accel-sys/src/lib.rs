@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 7;
+pub const SHD_ABI_VERSION: u32 = 8;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -24,6 +24,8 @@ pub const SHD_TB_SKIPPED: u32 = 2;
 pub const SHD_TB_EXEMPT: u32 = 1;
 pub const SHD_INBOUND_FORWARDED: u32 = 1;
 pub const SHD_INBOUND_DROPPED: u32 = 2;
+pub const SHD_QDISC_FIFO: u32 = 0;
+pub const SHD_QDISC_ROUND_ROBIN: u32 = 1;
 pub const SHD_OK: shd_status = 0;
 pub const SHD_ERR_NO_EDGE: shd_status = 1;
 pub const SHD_ERR_MULTI_EDGE: shd_status = 2;
@@ -231,9 +233,11 @@ extern "C" {
     pub fn shd_inbound_advance(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_size: *const u32, d_pkt: *const u32, n_events: u64, window_end: u64, bootstrap_end: u64, out_off: *mut *const u32, out_pkt: *mut *const u32, out_time: *mut *const u64, out_kind: *mut *const u8, n_out: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
     pub fn shd_inbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, codel: *mut shd_codel_state, bucket: *mut shd_tb_state) -> shd_status;
     pub fn shd_outbound_setup(ctx: *mut shd_ctx, n_hosts: u32, first_host: u32, capacity: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
+    pub fn shd_outbound_setup_qdisc(ctx: *mut shd_ctx, n_hosts: u32, first_host: u32, capacity: u32, qdisc: u32, max_sockets: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
     pub fn shd_outbound_advance(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, bootstrap_end: u64, d_batch_out: *mut shd_batch, sent_pkt: *mut *const u32, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
     pub fn shd_outbound_sent_sizes(ctx: *mut shd_ctx, d_size: *mut *const u32) -> shd_status;
     pub fn shd_outbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, queue_len: *mut u32, head_pkt: *mut u32, bucket: *mut shd_tb_state) -> shd_status;
+    pub fn shd_outbound_get_sockets(ctx: *mut shd_ctx, host: u32, handles: *mut u64, counts: *mut u32, cap: u32, n_sockets: *mut u32) -> shd_status;
     pub fn shd_ledger_setup(ctx: *mut shd_ctx, max_live_batches: u32) -> shd_status;
     pub fn shd_ledger_record(ctx: *mut shd_ctx, batch: u64, d_size: *const u32, d_pkt: *const u32, n_packets: u64, n_live: u64) -> shd_status;
     pub fn shd_ledger_record_sharded(ctx: *mut shd_ctx, batch: u64, d_size: *const u32, d_pkt: *const u32, d_dst_host: *const u32, d_status: *const u8, n_packets: u64, d_out: *mut shd_relay_out, local: shd_status) -> shd_status;

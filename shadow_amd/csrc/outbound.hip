@@ -1,5 +1,5 @@
-// The outbound stage on the GPU: per source host the network interface's FIFO queuing discipline,
-// the outbound relay's token bucket and the relay's own state, device-resident across calls.  One
+// The outbound stage on the GPU: per source host the network interface's queuing discipline (FIFO
+// or round-robin: interface_qdisc, configuration.rs:396-397), the outbound relay's token bucket and the relay's own state, device-resident across calls.  One
 // call advances every host over one scheduling window, lane per host, from the window's offers
 // ("socket data became sendable") to the instant each packet enters Worker::send_packet: the
 // shd_batch a relay round (relay.hip) takes, with no CPU step in between.
@@ -11,6 +11,8 @@
 //     :604-610 get_next_packet_priority: one counter per host, so priorities are unique per host
 //   src/main/host/network/network_interface.c
 //     :276-316 _networkinterface_selectFifo: the socket whose head packet has the lowest priority
+//     :235-273 _networkinterface_selectRoundRobin, :366-392 networkinterface_wantsSend: the
+//              rrQueue (rr_queue.h restates both)
 //   src/main/host/network/network_queuing_disciplines.c
 //     :90-102  the FIFO comparison of two sockets' head priorities (never equal)
 //   src/main/network/relay/mod.rs
@@ -43,9 +45,16 @@
 // packet is never overtaken, not by a local packet and not by a lower priority (head-of-line
 // blocking, as the reference).
 //
-// Not covered: the round-robin discipline (network_interface.c:235-273; FIFO is the default,
-// configuration.rs:495), the loopback relay (unlimited, every packet local), the pcap and tracker
-// side effects of networkinterface_pop, and the CPU-delay model (as the inbound stage).
+// Under round-robin (OutRr below) "insert by priority" reads "offer to the socket's packets" and
+// the 64-bit key is the socket's canonical handle; the merge is then exact whenever a host's
+// offers at one instant belong to one event (one accumulation under relay/mod.rs:124-126) or to
+// one socket.  Two events on one host at the same nanosecond that offer on different sockets are
+// rotated together here; in the reference the first event's task may already have drained its
+// packets.  Within a socket packets leave in offer order: the separate control buffer
+// (socket.c:467) is not modelled.
+//
+// Not covered: the loopback relay (unlimited, every packet local), the pcap and tracker side
+// effects of networkinterface_pop, and the CPU-delay model (as the inbound stage).
 //
 // Each packet leaves the stage at most once, as one record: SENT (pkt, time, dst, payload, size) or
 // LOCAL (pkt, time).  Host h owns a region of (its offers + queued + cached) records, bounded by a
@@ -60,6 +69,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "rr_queue.h"
 #include "scan.h"
 #include "tbucket_ops.h"
 
@@ -87,7 +97,8 @@ constexpr uint32_t kOutRingFull = 8u;
 constexpr uint32_t kOutPanic = 16u;     // where the reference panics (token_bucket.rs unwraps)
 constexpr uint32_t kOutSpin = 32u;      // the task budget ran out (unreachable under the input contract)
 constexpr uint32_t kOutRegion = 64u;    // a record past the host's region (unreachable: one record per packet)
-constexpr uint32_t kOutBadPrio = 128u;  // a priority equal to one still queued on the host
+constexpr uint32_t kOutBadPrio = 128u;  // a priority equal to one still queued on the host (FIFO)
+constexpr uint32_t kOutSockFull = 256u; // one socket more than max_sockets in a host's rrQueue (round-robin)
 
 struct OutPkt {   // 24 bytes: a queued packet
     uint64_t prio;
@@ -106,6 +117,154 @@ struct OutRelay {   // 72 bytes per host
     uint32_t has_cached, cached_pkt, cached_size, cached_payload, cached_dst, pad;   // RelayInternal::next_packet
 };
 static_assert(sizeof(OutRelay) == 72, "OutRelay layout");
+
+// The queuing discipline behind outb_run (configuration.rs:396-397, QDiscMode): what an offer
+// does to the host's queue and which packet a pop takes.  Everything else -- the merge with the
+// forward task, the cached packet, the bucket, the records -- is the kernel's, once.  A policy is
+// built per lane from the kernel's arguments and the host's relay words; insert returns status
+// bits (0: taken), pop needs R.count >= 1, store puts the policy's own words back.  Both keep
+// R.count (packets queued) and R.head_* (the packet the next pop takes) current:
+// shd_outbound_get_state and outb_count read them for either discipline.
+
+// FIFO (network_interface.c:276-316): the lowest priority queued, a sorted ring per host.
+struct OutFifo {
+    struct Args {
+        OutPkt* ring_all;
+        uint32_t cap;
+    };
+    OutPkt* ring;
+    uint32_t cap;
+    __device__ __forceinline__ OutFifo(const Args& a, uint32_t h, const OutRelay&)
+        : ring(a.ring_all + (size_t)h * a.cap), cap(a.cap) {}
+    __device__ __forceinline__ uint32_t insert(OutRelay& R, const OutPkt& e) {
+        if (R.count == cap) return kOutRingFull;
+        if (R.count == 0) {
+            R.head_prio = e.prio;
+            R.head_pkt = e.pkt;
+            R.head_size = e.size;
+            R.head_payload = e.payload;
+            R.head_dst = e.dst;
+            R.tail_prio = e.prio;
+        } else if (e.prio == R.head_prio || e.prio == R.tail_prio) {
+            return kOutBadPrio;
+        } else if (e.prio < R.head_prio) {   // the new first packet: the old one goes in front of the ring
+            R.head = R.head == 0 ? cap - 1 : R.head - 1;
+            ring[R.head] = OutPkt{R.head_prio, R.head_pkt, R.head_size, R.head_payload, R.head_dst};
+            R.head_prio = e.prio;
+            R.head_pkt = e.pkt;
+            R.head_size = e.size;
+            R.head_payload = e.payload;
+            R.head_dst = e.dst;
+        } else {
+            // behind the ring's last packet; the priorities in arrival order (e.prio above
+            // tail_prio) append without a read, any other shifts the larger ones up.  The
+            // shift stops inside the ring at the latest at its start: e.prio > head_prio.
+            uint32_t pos = R.count - 1;   // packets in the ring
+            if (e.prio > R.tail_prio) {
+                R.tail_prio = e.prio;
+            } else {
+                bool dup = false;
+                while (pos > 0) {
+                    uint32_t j = R.head + pos - 1;
+                    if (j >= cap) j -= cap;
+                    const OutPkt q = ring[j];
+                    if (q.prio <= e.prio) {
+                        dup = q.prio == e.prio;   // where the shift stopped
+                        break;
+                    }
+                    uint32_t j1 = j + 1;
+                    if (j1 == cap) j1 = 0;
+                    ring[j1] = q;
+                    --pos;
+                }
+                if (dup) return kOutBadPrio;
+            }
+            uint32_t j = R.head + pos;
+            if (j >= cap) j -= cap;
+            ring[j] = e;
+        }
+        ++R.count;
+        return 0;
+    }
+    __device__ __forceinline__ void pop(OutRelay& R, uint32_t& p_, uint32_t& s_, uint32_t& pl_, uint32_t& d_) {
+        p_ = R.head_pkt;           // the lowest priority queued
+        s_ = R.head_size;
+        pl_ = R.head_payload;
+        d_ = R.head_dst;
+        if (--R.count) {           // the next one moves up from the ring
+            const OutPkt q = ring[R.head];
+            R.head = R.head + 1 == cap ? 0 : R.head + 1;
+            R.head_prio = q.prio;
+            R.head_pkt = q.pkt;
+            R.head_size = q.size;
+            R.head_payload = q.payload;
+            R.head_dst = q.dst;
+        }
+    }
+    __device__ __forceinline__ void store(OutRelay&) {}
+};
+
+// Round-robin (network_interface.c:235-273): rr_queue.h's queue, the functions
+// tests/rr_queue_main.cpp compiles.  The offer's 64-bit key is the socket's canonical handle.  The
+// queue's words live in the relay words the FIFO form uses for its own -- head_prio: the head
+// socket's handle; head_*: its first packet; tail_prio: the first and last slot of its further
+// packets; head, pad: the socket ring's start and length -- so outb_count and
+// shd_outbound_get_state serve both; the pool's two words (bump count, free list) lie in an array
+// of their own.
+struct OutRr {
+    struct Args {
+        RrSlot* pool_all;
+        RrSock* socks_all;
+        uint2* words_all;
+        uint32_t cap, max_sockets;
+    };
+    RrQueue q;
+    RrSlot* pool;
+    RrSock* socks;
+    uint2* pw;
+    uint32_t cap, max_sockets;
+    static __host__ __device__ __forceinline__ void unpack(const OutRelay& R, uint2 w, RrQueue& q) {
+        q.handle = R.head_prio;
+        q.pkt = R.head_pkt;
+        q.size = R.head_size;
+        q.payload = R.head_payload;
+        q.dst = R.head_dst;
+        q.first = (uint32_t)R.tail_prio;
+        q.last = (uint32_t)(R.tail_prio >> 32);
+        q.count = R.count;
+        q.ring_head = R.head;
+        q.ring_count = R.pad;
+        q.bump = w.x;
+        q.free = w.y;
+    }
+    __device__ __forceinline__ OutRr(const Args& a, uint32_t h, const OutRelay& R)
+        : pool(a.pool_all + (size_t)h * a.cap), socks(a.socks_all + (size_t)h * a.max_sockets),
+          pw(a.words_all + h), cap(a.cap), max_sockets(a.max_sockets) {
+        unpack(R, *pw, q);
+    }
+    __device__ __forceinline__ uint32_t insert(OutRelay& R, const OutPkt& e) {
+        const RrOffer o = rr_offer(q, pool, cap, socks, max_sockets, e.prio, e.pkt, e.size, e.payload, e.dst);
+        if (o != kRrOk) return o == kRrPoolFull ? kOutRingFull : kOutSockFull;
+        R.count = q.count;   // (the one word the kernel's own code reads between the calls)
+        return 0;
+    }
+    __device__ __forceinline__ void pop(OutRelay& R, uint32_t& p_, uint32_t& s_, uint32_t& pl_, uint32_t& d_) {
+        rr_pop(q, pool, socks, max_sockets, p_, s_, pl_, d_);
+        R.count = q.count;
+    }
+    __device__ __forceinline__ void store(OutRelay& R) {
+        R.count = q.count;
+        R.head_pkt = q.pkt;
+        R.head_size = q.size;
+        R.head_payload = q.payload;
+        R.head_dst = q.dst;
+        R.head_prio = q.handle;
+        R.tail_prio = (uint64_t)q.first | ((uint64_t)q.last << 32);
+        R.head = q.ring_head;
+        R.pad = q.ring_count;
+        *pw = make_uint2(q.bump, q.free);
+    }
+};
 
 // cnt[h] = the records host h can write: its offers + queued + cached; cnt[n_hosts] = 0 (the scan's
 // total).  Offsets that are not a CSR over n_offers offers are reported and count as no offers.
@@ -131,10 +290,11 @@ __global__ __launch_bounds__(256) void outb_count(uint32_t n_hosts, const uint32
     cnt[h] = no + rl[h].count + rl[h].has_cached;
 }
 
+template <class Q>
 __global__ __launch_bounds__(kOutLanes) void outb_run(
     uint32_t n_hosts, uint32_t first_host, const uint32_t* __restrict__ off, const uint64_t* __restrict__ time,
     const uint64_t* __restrict__ prio, const uint32_t* __restrict__ size, const uint32_t* __restrict__ payload,
-    const uint32_t* __restrict__ dst, const uint32_t* __restrict__ pkt, OutPkt* ring_all, uint32_t cap, TbRelay* tb,
+    const uint32_t* __restrict__ dst, const uint32_t* __restrict__ pkt, const typename Q::Args qa, TbRelay* tb,
     OutRelay* rl, const uint32_t* __restrict__ reg_off, uint32_t* __restrict__ nsent, uint32_t* __restrict__ nloc,
     uint32_t* r_pkt, uint64_t* r_time, uint32_t* r_dst, uint32_t* r_pay, uint32_t* r_size, uint64_t prev_end,
     uint64_t window_end,
@@ -154,9 +314,9 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
     uint32_t n_s = 0, n_l = 0, stored = 0;
     uint64_t task_min = kOutIdle;
     if (live) {
-        OutPkt* ring = ring_all + (size_t)h * cap;
         TbRelay B = tb[h];
         OutRelay R = rl[h];
+        Q q(qa, h, R);   // the discipline's queue: its part of R, its arrays
         const uint32_t self = first_host + h;   // the host's global id: what "local" compares with
         const uint32_t r_lo = reg_off[h], r_hi = reg_off[h + 1];
         uint32_t k = off ? off[h] : 0u;
@@ -216,60 +376,10 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
                     err |= kOutBadPkt;
                     break;
                 }
-                if (R.count == cap) {
-                    err |= kOutRingFull;
+                if (const uint32_t refused = q.insert(R, e)) {
+                    err |= refused;
                     break;
                 }
-                if (R.count == 0) {
-                    R.head_prio = e.prio;
-                    R.head_pkt = e.pkt;
-                    R.head_size = e.size;
-                    R.head_payload = e.payload;
-                    R.head_dst = e.dst;
-                    R.tail_prio = e.prio;
-                } else if (e.prio == R.head_prio || e.prio == R.tail_prio) {
-                    err |= kOutBadPrio;
-                    break;
-                } else if (e.prio < R.head_prio) {   // the new first packet: the old one goes in front of the ring
-                    R.head = R.head == 0 ? cap - 1 : R.head - 1;
-                    ring[R.head] = OutPkt{R.head_prio, R.head_pkt, R.head_size, R.head_payload, R.head_dst};
-                    R.head_prio = e.prio;
-                    R.head_pkt = e.pkt;
-                    R.head_size = e.size;
-                    R.head_payload = e.payload;
-                    R.head_dst = e.dst;
-                } else {
-                    // behind the ring's last packet; the priorities in arrival order (e.prio above
-                    // tail_prio) append without a read, any other shifts the larger ones up.  The
-                    // shift stops inside the ring at the latest at its start: e.prio > head_prio.
-                    uint32_t pos = R.count - 1;   // packets in the ring
-                    if (e.prio > R.tail_prio) {
-                        R.tail_prio = e.prio;
-                    } else {
-                        bool dup = false;
-                        while (pos > 0) {
-                            uint32_t j = R.head + pos - 1;
-                            if (j >= cap) j -= cap;
-                            const OutPkt q = ring[j];
-                            if (q.prio <= e.prio) {
-                                dup = q.prio == e.prio;   // where the shift stopped
-                                break;
-                            }
-                            uint32_t j1 = j + 1;
-                            if (j1 == cap) j1 = 0;
-                            ring[j1] = q;
-                            --pos;
-                        }
-                        if (dup) {
-                            err |= kOutBadPrio;
-                            break;
-                        }
-                    }
-                    uint32_t j = R.head + pos;
-                    if (j >= cap) j -= cap;
-                    ring[j] = e;
-                }
-                ++R.count;
                 last_t = t_of;
                 if (R.task == kOutIdle) R.task = t_of;   // Relay::notify: forward_later(ZERO)
                 ++k;
@@ -292,19 +402,7 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
                         R.has_cached = 0;
                     } else {
                         if (R.count == 0) break;   // ran out of packets: Idle
-                        p_ = R.head_pkt;           // the lowest priority queued
-                        s_ = R.head_size;
-                        pl_ = R.head_payload;
-                        d_ = R.head_dst;
-                        if (--R.count) {           // the next one moves up from the ring
-                            const OutPkt q = ring[R.head];
-                            R.head = R.head + 1 == cap ? 0 : R.head + 1;
-                            R.head_prio = q.prio;
-                            R.head_pkt = q.pkt;
-                            R.head_size = q.size;
-                            R.head_payload = q.payload;
-                            R.head_dst = q.dst;
-                        }
+                        q.pop(R, p_, s_, pl_, d_);   // networkinterface_pop
                     }
                     const bool local = d_ == self;   // relay/mod.rs:222-230
                     if (!boot && !local && B.capacity) {
@@ -345,6 +443,7 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
         }
         if (bad) err |= kOutPanic;
         if (err) atomicOr(status, err);
+        q.store(R);
         tb[h] = B;
         rl[h] = R;
         nsent[h] = n_s;
@@ -417,10 +516,15 @@ using namespace shd;
 
 extern "C" {
 
-shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
-                              const uint64_t* tb_capacity, const uint64_t* tb_refill_increment,
-                              const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill) {
+shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
+                                    uint32_t qdisc, uint32_t max_sockets, const uint64_t* tb_capacity,
+                                    const uint64_t* tb_refill_increment, const uint64_t* tb_refill_interval_ns,
+                                    const uint64_t* tb_last_refill) {
     if (!ctx || capacity == 0) return SHD_ERR_INVALID;
+    if (qdisc != SHD_QDISC_FIFO && qdisc != SHD_QDISC_ROUND_ROBIN) return SHD_ERR_INVALID;
+    const bool rr = qdisc == SHD_QDISC_ROUND_ROBIN;
+    // (slot and ring indices are summed in 32 bits before they wrap)
+    if (rr && (max_sockets == 0 || max_sockets > 0x7FFFFFFFu || capacity > 0x7FFFFFFFu)) return SHD_ERR_INVALID;
     if ((uint64_t)first_host + n_hosts > 0xFFFFFFFFull) return SHD_ERR_INVALID;   // global ids are u32
     std::vector<TbRelay> hb;
     SHD_TRY(tb_rows(n_hosts, tb_capacity, tb_refill_increment, tb_refill_interval_ns, tb_last_refill, hb));
@@ -429,7 +533,11 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
     hipStream_t s = ctx->stream;
     SHD_HIP(hipSetDevice(ctx->device));
     const size_t n1 = std::max<size_t>(n_hosts, 1);
-    SHD_TRY(O.ring.ensure(std::max<size_t>((size_t)n_hosts * capacity, 1) * sizeof(OutPkt)));
+    SHD_TRY(O.ring.ensure(std::max<size_t>((size_t)n_hosts * capacity, 1) * (rr ? sizeof(RrSlot) : sizeof(OutPkt))));
+    if (rr) {
+        SHD_TRY(O.socks.ensure(std::max<size_t>((size_t)n_hosts * max_sockets, 1) * sizeof(RrSock)));
+        SHD_TRY(O.rr_words.ensure(n1 * sizeof(uint2)));
+    }
     SHD_TRY(O.tb.ensure(n1 * sizeof(TbRelay)));
     SHD_TRY(O.rl.ensure(n1 * sizeof(OutRelay)));
     SHD_TRY(O.cnt.ensure(((size_t)n_hosts + 1) * 4));
@@ -443,6 +551,10 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
     OutRelay idle{};
     idle.task = kOutIdle;
     const std::vector<OutRelay> hr(n_hosts, idle);
+    // an empty pool: nothing bumped, no free slot; its links are written as slots are freed
+    const std::vector<uint2> hw(rr ? n_hosts : 0, make_uint2(0, kRrNil));
+    if (!hw.empty())
+        SHD_HIP(hipMemcpyAsync(O.rr_words.p, hw.data(), hw.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
     if (n_hosts) {
         SHD_HIP(hipMemcpyAsync(O.tb.p, hb.data(), (size_t)n_hosts * sizeof(TbRelay), hipMemcpyHostToDevice, s));
         SHD_HIP(hipMemcpyAsync(O.rl.p, hr.data(), (size_t)n_hosts * sizeof(OutRelay), hipMemcpyHostToDevice, s));
@@ -451,11 +563,20 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
     O.n_hosts = n_hosts;
     O.first_host = first_host;
     O.cap = capacity;
+    O.round_robin = rr;
+    O.max_sockets = rr ? max_sockets : 0;
     O.n_stored = 0;
     O.prev_end = 0;
     O.advanced = false;
     O.ready = true;
     return SHD_OK;
+}
+
+shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
+                              const uint64_t* tb_capacity, const uint64_t* tb_refill_increment,
+                              const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill) {
+    return shd_outbound_setup_qdisc(ctx, n_hosts, first_host, capacity, SHD_QDISC_FIFO, 0, tb_capacity,
+                                    tb_refill_increment, tb_refill_interval_ns, tb_last_refill);
 }
 
 shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
@@ -502,11 +623,19 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
                                                                 nloc, reinterpret_cast<uint32_t*>(words));
         SHD_HIP(hipGetLastError());
         SHD_TRY(scan_excl2(O.scan, cnt, cnt, nullptr, nullptr, (uint64_t)H + 1, s));   // -> region offsets
-        outb_run<<<div_up(H, kOutLanes), kOutLanes, 0, s>>>(H, O.first_host, off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt,
-                                                O.ring.as<OutPkt>(), O.cap, O.tb.as<TbRelay>(), O.rl.as<OutRelay>(),
-                                                cnt, nsent, nloc, O.r_pkt.as<uint32_t>(), O.r_time.as<uint64_t>(),
-                                                O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.r_size.as<uint32_t>(),
-                                                O.prev_end, window_end, bootstrap_end, words);
+        // one kernel, two instances: the discipline is the queue policy alone
+        auto run = [&](auto kernel, auto qa) {
+            kernel<<<div_up(H, kOutLanes), kOutLanes, 0, s>>>(
+                H, O.first_host, off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, qa, O.tb.as<TbRelay>(),
+                O.rl.as<OutRelay>(), cnt, nsent, nloc, O.r_pkt.as<uint32_t>(), O.r_time.as<uint64_t>(),
+                O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.r_size.as<uint32_t>(), O.prev_end, window_end,
+                bootstrap_end, words);
+        };
+        if (O.round_robin)
+            run(outb_run<OutRr>, OutRr::Args{O.ring.as<RrSlot>(), O.socks.as<RrSock>(), O.rr_words.as<uint2>(), O.cap,
+                                             O.max_sockets});
+        else
+            run(outb_run<OutFifo>, OutFifo::Args{O.ring.as<OutPkt>(), O.cap});
         SHD_HIP(hipGetLastError());
         // the sent and the local counts per host, both in one launch -> src_off, loc_off
         SHD_TRY(scan_excl2(O.scan, nsent, O.src_off.as<uint32_t>(), nloc, O.loc_off.as<uint32_t>(), (uint64_t)H + 1, s));
@@ -586,6 +715,31 @@ shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_ti
         bucket->last_refill = b.last_refill;
         bucket->pending_until = r.task == kOutIdle ? 0 : r.task;   // the relay's task, as shd_tb_state names it
     }
+    return SHD_OK;
+}
+
+shd_status shd_outbound_get_sockets(shd_ctx* ctx, uint32_t host, uint64_t* handles, uint32_t* counts, uint32_t cap,
+                                    uint32_t* n_sockets) {
+    if (!ctx) return SHD_ERR_INVALID;
+    OutboundState& O = ctx->outb;
+    if (!O.ready || !O.round_robin) return SHD_ERR_STATE;   // (a FIFO stage has no rrQueue)
+    if (host >= O.n_hosts || (cap && (!handles || !counts))) return SHD_ERR_INVALID;
+    SHD_HIP(hipSetDevice(ctx->device));
+    // the host's words, its pool and its socket ring; the chains are walked here by rr_queue.h
+    OutRelay r;
+    uint2 w;
+    std::vector<RrSlot> pool(O.cap);
+    std::vector<RrSock> socks(O.max_sockets);
+    SHD_HIP(hipMemcpy(&r, O.rl.as<OutRelay>() + host, sizeof(r), hipMemcpyDeviceToHost));
+    SHD_HIP(hipMemcpy(&w, O.rr_words.as<uint2>() + host, sizeof(w), hipMemcpyDeviceToHost));
+    SHD_HIP(hipMemcpy(pool.data(), O.ring.as<RrSlot>() + (size_t)host * O.cap, pool.size() * sizeof(RrSlot),
+                      hipMemcpyDeviceToHost));
+    SHD_HIP(hipMemcpy(socks.data(), O.socks.as<RrSock>() + (size_t)host * O.max_sockets,
+                      socks.size() * sizeof(RrSock), hipMemcpyDeviceToHost));
+    RrQueue q;
+    OutRr::unpack(r, w, q);
+    const uint32_t n = rr_counts(q, pool.data(), O.cap, socks.data(), O.max_sockets, handles, counts, cap);
+    if (n_sockets) *n_sockets = n;
     return SHD_OK;
 }
 

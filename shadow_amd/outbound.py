@@ -1,15 +1,18 @@
 """Host-side mirror of the outbound stage (``shd_outbound_*``): per source host the network
-interface's FIFO queue, the outbound relay's token bucket and the relay's state, kept on the
-MI355X engine.
+interface's queue under either queuing discipline (``interface_qdisc``: FIFO or round-robin), the
+outbound relay's token bucket and the relay's state, kept on the MI355X engine.
 
 Restates the outbound relay ``relay_inet_out`` (``src/main/host/host.rs:285-288``, ``:871-880``)
 for every host at once: the interface's FIFO queuing discipline picks the packet of the lowest
 priority (``network_interface.c:276-316``), ``Relay::forward_until_blocked``
 (``relay/mod.rs:200-272``) takes tokens from the ``bw_up`` bucket, and a packet that conforms enters
-``Worker::send_packet`` at the task's time (``router/mod.rs:49-55``).
+``Worker::send_packet`` at the task's time (``router/mod.rs:49-55``).  With
+``qdisc="round-robin"`` the interface keeps the rrQueue instead (``network_interface.c:235-273``,
+``:366-392``): the sockets that have packets queued take turns, one packet each, and the per-offer
+key is the offering socket's canonical handle (``sock=`` where FIFO takes ``prio=``).
 
-``OutboundStage(engine, capacity, refill_increment, refill_interval, last_refill, first_host=0)``
--- bucket parameters per host, all three 0 for a host without a bucket; host ``h``'s global id is
+``OutboundStage(engine, capacity, refill_increment, refill_interval, last_refill, first_host=0,
+qdisc="fifo", max_sockets=64)`` -- bucket parameters per host, all three 0 for a host without a bucket; host ``h``'s global id is
 ``first_host + h`` -- or ``OutboundStage.from_bandwidth(engine, bytes_per_second, start)``.
 ``advance(off, time, prio, size, payload, dst, pkt, window_end=...)`` consumes one window's offers
 grouped by host (host arrays; ``advance_device`` takes them as they lie on the GPU) and returns the
@@ -28,6 +31,7 @@ from .tbucket import SIM_START, create_token_bucket
 
 IDLE = 2**64 - 1
 NO_PKT = 2**32 - 1
+QDISC = {"fifo": N.QDISC_FIFO, "round-robin": N.QDISC_ROUND_ROBIN}
 
 
 @dataclass
@@ -71,30 +75,39 @@ class Sent:
 
 class OutboundStage:
     def __init__(self, engine, capacity, refill_increment, refill_interval, last_refill=SIM_START,
-                 first_host: int = 0, ring_capacity: int = 4096):
+                 first_host: int = 0, ring_capacity: int = 4096, qdisc: str = "fifo", max_sockets: int = 64):
+        """``ring_capacity``: the packets a host may have queued; ``max_sockets`` (round-robin
+        only): the sockets it may have in its rrQueue at once."""
+        if qdisc not in QDISC:
+            raise ValueError(f"qdisc must be one of {sorted(QDISC)}, not {qdisc!r}")
         self.eng = engine
+        self.qdisc = qdisc
         cap = np.ascontiguousarray(capacity, np.uint64)
         self.n_hosts = len(cap)
         self.first_host = int(first_host)
         inc = np.ascontiguousarray(np.broadcast_to(np.asarray(refill_increment, np.uint64), cap.shape))
         itv = np.ascontiguousarray(np.broadcast_to(np.asarray(refill_interval, np.uint64), cap.shape))
         last = np.ascontiguousarray(np.broadcast_to(np.asarray(last_refill, np.uint64), cap.shape))
-        N.check(engine.lib.shd_outbound_setup(engine.ctx, self.n_hosts, self.first_host, int(ring_capacity),
-                                              N.ptr(cap), N.ptr(inc), N.ptr(itv), N.ptr(last)), "shd_outbound_setup")
+        self.max_sockets = int(max_sockets)
+        N.check(engine.lib.shd_outbound_setup_qdisc(engine.ctx, self.n_hosts, self.first_host, int(ring_capacity),
+                                                    QDISC[qdisc], self.max_sockets, N.ptr(cap), N.ptr(inc),
+                                                    N.ptr(itv), N.ptr(last)), "shd_outbound_setup_qdisc")
 
     @classmethod
     def from_bandwidth(cls, engine, bytes_per_second, start: int = SIM_START, first_host: int = 0,
-                       ring_capacity: int = 4096):
+                       ring_capacity: int = 4096, qdisc: str = "fifo", max_sockets: int = 64):
         """One ``create_token_bucket`` (relay/mod.rs:291-302) of ``bw_up / 8`` bytes per second per
         host, last refilled at ``start``; an entry of ``None`` (or a negative one) is a host without
         a bucket."""
         rows = [(0, 0, 0) if b is None or int(b) < 0 else create_token_bucket(int(b)) for b in bytes_per_second]
         cap, inc, itv = (np.array([r[i] for r in rows], np.uint64) for i in range(3))
-        return cls(engine, cap, inc, itv, start, first_host, ring_capacity)
+        return cls(engine, cap, inc, itv, start, first_host, ring_capacity, qdisc, max_sockets)
 
     def advance_device(self, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers: int,
                        window_end: int, bootstrap_end: int = 0) -> DeviceBatch:
-        """Device pointers (ints, ctypes pointers or torch tensors; all None for no offers)."""
+        """Device pointers (ints, ctypes pointers or torch tensors; all None for no offers).
+        ``d_prio`` is the discipline's 64-bit key per offer: the packet priority under FIFO, the
+        socket's canonical handle under round-robin."""
         as_p = lambda a: a if a is None or isinstance(a, (int, C.c_void_p)) else N.ptr(a)  # noqa: E731
         b = N.Batch()
         sp, lo, lp, lt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -107,8 +120,14 @@ class OutboundStage:
                            nxt.value)
 
     def advance(self, off=None, time=None, prio=None, size=None, payload=None, dst=None, pkt=None, *,
-                window_end: int, bootstrap_end: int = 0) -> Sent:
-        """Host arrays of one window's offers grouped by host (or none) -> host copies."""
+                window_end: int, bootstrap_end: int = 0, sock=None) -> Sent:
+        """Host arrays of one window's offers grouped by host (or none) -> host copies.  ``sock``
+        (the offering sockets' canonical handles) is the round-robin spelling of ``prio``: the
+        same column; giving both is an error."""
+        if sock is not None:
+            if prio is not None:
+                raise ValueError("prio and sock name the same column: give one")
+            prio = sock
         keep = [None] * 7
         n = 0
         if off is not None:
@@ -137,9 +156,17 @@ class OutboundStage:
                         "shd_copy_to_host")
         return Sent(src_off, t, d, p, sp, loc_off, lp, lt, out.n_stored, out.next_task_time)
 
+    def sockets(self, host: int) -> list:
+        """One host's rrQueue in order: ``[(handle, queued packets), ...]``.  Round-robin only."""
+        hd, cn = np.zeros(self.max_sockets, np.uint64), np.zeros(self.max_sockets, np.uint32)
+        n = C.c_uint32(0)
+        N.check(self.eng.lib.shd_outbound_get_sockets(self.eng.ctx, int(host), N.ptr(hd), N.ptr(cn), len(hd),
+                                                      C.byref(n)), "shd_outbound_get_sockets")
+        return list(zip(hd[:n.value].tolist(), cn[:n.value].tolist()))
+
     def state(self, host: int) -> dict:
         """One host: ``task_time`` (None: Idle), ``cached`` ((pkt, size) or None), ``queue_len``,
-        ``head_pkt`` (the lowest priority queued, None: empty) and the bucket as
+        ``head_pkt`` (the packet the next pop takes, None: empty) and the bucket as
         ``TokenBuckets.state`` (None: no bucket)."""
         task, has, cp, cs = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         ql, hp, b = C.c_uint32(0), C.c_uint32(0), N.TbState()

@@ -2,14 +2,17 @@
 the same host and event counts and the same window shape.
 
     python tools/outbound_window.py [--hosts 100000] [--per-host 100] [--windows 8] [--slow-share 0.5]
-                                    [--local-share 0.0] [--swap-share 0.0]
+                                    [--local-share 0.0] [--swap-share 0.0] [--qdisc fifo|rr] [--sockets 4]
 
 Every host gets about --per-host offers per 1 ms window (sizes 20% 52 B / 60% 1500 B / 20% uniform,
 times sorted per host, priorities in arrival order, destinations uniform), generated on the device.
 --slow-share of the hosts have a 10 MB/s bucket (their packets block, queue up and carry from
 window to window), the rest the reference's default 1 Gbit/s (125 MB/s).  --local-share of the
 offers go to the offering host itself; --swap-share of the offers trade priorities with their
-neighbour (inserts that shift).  Each window is one shd_outbound_advance, timed with the host clock
+neighbour (inserts that shift).  --qdisc rr sets the stage up with the round-robin discipline:
+each host's offers are spread over --sockets handles (uniformly, the handle in the priority
+column), and --ring is still the packets a host may have queued.  Each window is one
+shd_outbound_advance, timed with the host clock
 around the call (it returns after its pinned read-back); the first two windows are warm-up.
 Prints one JSON line."""
 from __future__ import annotations
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--local-share", type=float, default=0.0)
     ap.add_argument("--swap-share", type=float, default=0.0)
     ap.add_argument("--ring", type=int, default=1024)
+    ap.add_argument("--qdisc", choices=["fifo", "rr"], default="fifo")
+    ap.add_argument("--sockets", type=int, default=4)
     a = ap.parse_args()
 
     import torch
@@ -62,7 +67,9 @@ def main():
                                                                                    device="cuda")))
         idx = torch.arange(n, device="cuda")
         prio = idx + (w << 32)               # increasing per host and across windows
-        if a.swap_share > 0:                 # neighbours of one host trade priorities
+        if a.qdisc == "rr":                  # the column is the socket's handle: host << 16 | one of K
+            prio = (host << 16) | torch.randint(0, a.sockets, (n,), generator=g, device="cuda")
+        if a.swap_share > 0 and a.qdisc == "fifo":   # neighbours of one host trade priorities
             first = torch.repeat_interleave(off[:-1], cnt)
             even = ((idx - first) & 1) == 0
             last = idx + 1 >= torch.repeat_interleave(off[1:], cnt)
@@ -77,7 +84,9 @@ def main():
 
     rates = [10_000_000 if h < a.slow_share * H else 125_000_000 for h in range(H)]
     with Engine(0) as eng:
-        stage = OutboundStage.from_bandwidth(eng, rates, SIM_START, ring_capacity=a.ring)
+        stage = OutboundStage.from_bandwidth(eng, rates, SIM_START, ring_capacity=a.ring,
+                                             qdisc="round-robin" if a.qdisc == "rr" else "fifo",
+                                             max_sockets=max(a.sockets, 1))
         ms, outs, n_ops = [], [], 0
         start = SIM_START
         for w in range(a.windows):
@@ -90,7 +99,8 @@ def main():
             n_ops = n
             start += MS
     timed = ms[2:] if len(ms) > 2 else ms
-    print(json.dumps({"hosts": H, "offers_per_window": n_ops, "slow_share": a.slow_share,
+    print(json.dumps({"hosts": H, "offers_per_window": n_ops, "qdisc": a.qdisc,
+                      "sockets": a.sockets if a.qdisc == "rr" else None, "slow_share": a.slow_share,
                       "local_share": a.local_share, "swap_share": a.swap_share,
                       "outbound_ms": [round(x, 3) for x in ms],
                       "outbound_ms_median": round(statistics.median(timed), 3),
