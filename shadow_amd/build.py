@@ -10,7 +10,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("routing.hip", "blocked.hip", "relay.hip", "api.cpp", "gml.cpp",
+SRC = [os.path.join(HERE, "csrc", f) for f in ("routing.hip", "blocked.hip", "relay.hip", "relay_radix.hip", "relay_wide.hip",
+                                                "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue.hip",
                                                 "hosts.cpp", "rounds.hip", "flush.hip", "inbound.hip",
                                                 "outbound.hip", "ledger.hip", "window.cpp")]

@@ -14,7 +14,6 @@ shd_status routing_prepare_impl(shd_ctx* ctx, const shd_graph* g, const uint32_t
                                 uint32_t n_used, uint32_t mode, shd_error* err);
 shd_status routing_run_impl(shd_ctx* ctx, uint32_t algo, uint32_t rb, uint32_t re,
                             uint64_t* d_lat, float* d_loss, shd_error* err);
-shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
 }  // namespace shd
 
 using namespace shd;
@@ -176,11 +175,6 @@ shd_ctx* shd_open(int device_ordinal, shd_status* st) {
             shd_close(ctx);
             return fail(SHD_ERR_HIP);
         }
-    for (auto& e : ctx->sev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            shd_close(ctx);
-            return fail(SHD_ERR_HIP);
-        }
     if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess) {
         ctx->side = nullptr;
         shd_close(ctx);
@@ -196,8 +190,6 @@ void shd_close(shd_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->side) (void)hipStreamSynchronize(ctx->side);
     for (auto& e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->sev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);

@@ -215,7 +215,7 @@ struct RelayState {
     bool table_narrow = false;  // every path latency < 2^32 ns -> 16-byte event records (v2)
     bool force_v1 = false;      // SHD_RELAY_FORCE_V1=1 (testing)
     bool force_v3 = false;      // SHD_RELAY_FORCE_V3=1 (testing): radix pipeline, not v7
-    int last_pipe = 0;          // pipeline of the last round: 1, 3 or 7
+    int last_pipe = 0;          // pipeline of the last round: 1, 3, 7 or 8
     bool count_on = true;       // per-path packet counters (RoutingInfo::increment_packet_count)
     bool last_v2 = false;
     uint64_t seq_bound = 0;     // >= every host's next event id
@@ -315,6 +315,9 @@ shd_status wait_marker(shd_ctx* ctx, hipStream_t s);
 // a committed relay round's (all-rank) reductions: the runahead update (runahead.rs:60-115) and
 // the earliest deliver time of the relay output that the queues have not merged yet (rounds.cpp)
 void round_note(shd_ctx* ctx, uint64_t min_deliver, uint64_t min_latency);
+// the smallest / largest of n device words (rounds.hip); one host synchronisation
+shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
+shd_status max_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
 // shd_relay_round_sharded with the caller's own status on entry (relay.hip): a failure is carried
 // into the round's status agreement -- the local pipeline is skipped, the round commits nowhere
 shd_status relay_round_sharded_local(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o,
@@ -332,7 +335,6 @@ struct shd_ctx {
     bool own_stream = false;
     hipEvent_t ev[8] = {};
     hipStream_t side = nullptr;        // second stream: work that overlaps the main stream's
-    hipEvent_t sev[2] = {};            // fork / join events (no timing)
     unsigned long long* h_pin = nullptr;   // shd::kPinWords pinned host words: flag / reduction read-backs
     shd::DevBuf g_one;                     // a device word holding 1 (shd::wait_stream's marker)
     bool spin_wait = true;                 // SHD_SPIN_WAIT=0: hipStreamSynchronize instead

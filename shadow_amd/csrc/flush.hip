@@ -10,7 +10,7 @@
 //   worker.rs:370), draw_hi = the source host's next_u64() >> 32 at send time.  gen::<f64>() is
 //   (next_u64 >> 11) * 2^-53 and consumes exactly one next_u64, so the CPU stream advances as in
 //   the reference; the top 32 bits decide `chance >= reliability` exactly for every reliability
-//   1f32 - loss (relay.hip draw_drops).
+//   1f32 - loss (relay_priv.h draw_drops).
 // The device turns the runs into the grouped layout the pipelines take (src_off, one contiguous
 // range per host in host order), runs the round with those draws (the device streams are left
 // untouched), and writes back per send a 2-bit status in stage order, and per event a 16-byte
@@ -19,15 +19,10 @@
 #include <algorithm>
 #include <cstring>
 
-#include "ctx.h"
+#include "relay_priv.h"
 #include "scan.h"
 
 namespace shd {
-
-// relay.hip: the round (pipelines + checks + commit) on a grouped device batch; the sharded
-// round on this rank's grouped sends
-shd_status relay_flush_round(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
-shd_status relay_flush_round_sharded(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
 
 struct Send12 {
     uint32_t time_off, dst, draw_hi;

@@ -1,9 +1,10 @@
-// Tuning and testing knobs of one context.  None changes a result: they pick grids, kernel
-// variants or an equivalent fallback pipeline -- except TEST_FAIL, fault injection for the
-// failure-agreement tests (1: a sharded relay round fails on this rank after its sizing summary
-// is read; 3: the host transport's staging cannot be allocated).  Each starts from the environment variable
-// SHD_<name>, read ONCE by shd_open, so a caller's environment cannot change grids between two
-// builds; shd_set_knob / shd_get_knob (api.cpp) change or inspect them per context afterwards.
+// Tuning and testing knobs of one context.  None that the environment reaches changes a result:
+// they pick grids, kernel variants or an equivalent fallback pipeline.  Each starts from the
+// environment variable SHD_<name>, read ONCE by shd_open, so a caller's environment cannot change
+// grids between two builds; shd_set_knob / shd_get_knob (api.cpp) change or inspect them per
+// context afterwards.  TEST_FAIL is fault injection for the failure-agreement tests (1: a sharded
+// relay round fails on this rank after its sizing summary is read; 3: the host transport's staging
+// cannot be allocated): only shd_set_knob sets it, the environment never does.
 #pragma once
 #include <stdint.h>
 
@@ -18,9 +19,9 @@ namespace shd {
     X(SSSP_RESERVE) X(FW_TILE) X(PRUNE_K) X(SSSP_REORDER) X(REORDER_MODE) X(SSSP_NO_SPREAD) X(SSSP_GLOBAL)        \
     X(SSSP_NO_DELTA) X(SSSP_DELTA) X(SSSP_STATS) X(SPIN_WAIT)                                   \
     X(PRUNE_DENSE_BUILD) X(PRUNE_STAGE2) X(SSSP_HUB) X(SYNC_KERNEL)                                               \
-    X(EQ_COUNT_BLOCKS) X(EQ_WAVE_MERGE) X(EQ_SEARCH_ONLY) X(EQ_MAX_RUNS) X(RELAY_GROUP_SENDS) X(HIST_SCALAR) X(B7_STOP) X(RELAY_FORCE_V1)         \
-    X(RELAY_FORCE_V3) X(RELAY_NO_LDS_MAP) X(MERGE_BY_EVENT) X(SHARD_CHUNK_ROWS) X(SHARD_REPLICATE_MB)             \
-    X(SHARD_RESERVE_SLOTS) X(RELAY_SHARD_X24) X(FLUSH_COPY) X(PRUNE_SHAPE) X(PRUNE_SHAPE_SH) X(EQ_FOLD) X(EQ_FOLD_TAKE) X(RELAY_K0_INLINE) X(RELAY_SCAN2)   \
+    X(EQ_COUNT_BLOCKS) X(EQ_WAVE_MERGE) X(EQ_SEARCH_ONLY) X(EQ_MAX_RUNS) X(RELAY_GROUP_SENDS) X(HIST_SCALAR) X(RELAY_FORCE_V1)         \
+    X(RELAY_FORCE_V3) X(RELAY_NO_LDS_MAP) X(SHARD_CHUNK_ROWS) X(SHARD_REPLICATE_MB)             \
+    X(SHARD_RESERVE_SLOTS) X(RELAY_SHARD_X24) X(FLUSH_COPY) X(PRUNE_SHAPE) X(PRUNE_SHAPE_SH) X(EQ_FOLD) X(EQ_FOLD_TAKE) X(RELAY_SCAN2)   \
     X(LEDGER_REMAP_SEARCH) X(TEST_FAIL)
 
 enum Knob : int {
@@ -54,7 +55,7 @@ struct Knobs {
             char var[64] = "SHD_";
             std::strncat(var, name(k), sizeof(var) - 5);
             const char* s = std::getenv(var);
-            v[k] = s && *s ? (int64_t)std::strtoull(s, nullptr, 10) : -1;
+            v[k] = k != K_TEST_FAIL && s && *s ? (int64_t)std::strtoull(s, nullptr, 10) : -1;
         }
     }
     uint32_t get(Knob k, uint32_t dflt) const { return v[k] < 0 ? dflt : (uint32_t)v[k]; }

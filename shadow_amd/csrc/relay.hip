@@ -1,23 +1,5 @@
-// Per-round inter-host packet relay on gfx950.
-//
-// Reference semantics, per staged send (FlyearthR/shadow src/main/core/worker.rs:328-413):
-//   now >= sim_end -> nothing happens (no RNG draw, no status)                      :334-341
-//   reliability = (1.0f32 - loss) as f64                                 WorkerShared :538-543
-//   chance = src_host.rng.gen::<f64>() = (xoshiro256++ >> 11) * 2^-53                  :365
-//   drop iff !bootstrapping && chance >= reliability && payload_size > 0              :370-378
-//   deliver = max(now + latency, round_end); next-event-time min; lowest-used-latency  :380-406
-//   event (deliver, Packet, src_host_id, src_host_event_id) into the dst queue  :408-411, 619-629
-// Destination order = EventQueue pop order (core/work/event.rs:84-155): time, then src host id,
-// then src event id.  Every event of round r has deliver >= round_end, so batching the whole
-// round to the barrier (core/manager.rs:455-464) is exact.
-//
-// Pipelines (one stream plus a side stream for K0, one host sync per round):
-//   7  K0 draws || bin histogram + scans; K1 stamp places every record into its destination
-//      bin (32 destinations); K4 bin_sort_v7 sorts each bin in LDS (decoupled look-back for
-//      the event offsets) and stores the events in order
-//   3  K0; K1 stamp writes records by packet; K2 radix sort by destination; K3 offsets; K4
-//      per-destination wave sort (fallback when a bin overflows pipeline 7's limits)
-//   1  64-bit records (path latencies >= 2^32 ns)
+// The relay round (overview and the list of units: relay_priv.h): K0, the stamps, pipelines 7 and
+// 8, the ladder over the pipelines, the commit and the relay's C entry points.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -26,286 +8,9 @@
 
 #include <vector>
 
-#include "scan.h"
-#include "wave.h"
+#include "relay_priv.h"
 
 namespace shd {
-
-constexpr uint32_t kStSkipped = 0, kStDropped = 1, kStSent = 2;
-
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-
-struct Xoshiro {
-    uint64_t s0, s1, s2, s3;
-    __device__ __forceinline__ uint64_t next() {
-        const uint64_t res = rotl64(s0 + s3, 23) + s0;
-        const uint64_t t = s1 << 17;
-        s2 ^= s0;
-        s3 ^= s1;
-        s1 ^= s2;
-        s0 ^= s3;
-        s2 ^= t;
-        s3 = rotl64(s3, 45);
-        return res;
-    }
-    // rand 0.8.5 Standard for f64: 53 high bits, multiply-based, [0, 1)
-    __device__ __forceinline__ double gen_f64() {
-        return (double)(next() >> 11) * (1.0 / 9007199254740992.0);
-    }
-};
-
-// chance >= reliability (worker.rs:365-370) from the draw's top 32 bits h = draw >> 32, which is
-// all K0 keeps (4 bytes per draw instead of 8).  chance = (draw >> 11) * 2^-53 exactly, so the
-// test is draw >> 11 >= T = ceil(reliability * 2^53) (exact: a power-of-two scale).  With
-// th = T >> 21 it is h >= th when T is a multiple of 2^21.  That always holds for a table loss
-// in [0, 1]: reliability = 1f32 - loss is >= 2^-9 (then reliability * 2^53 = m * 2^(e + 30),
-// e >= -9, a multiple of 2^21) or is 1 - loss for loss in [0.5, 1], a multiple of 2^-24 (T a
-// multiple of 2^29).  For any other value h > th decides unless h == th, where the low bits
-// would: `tie` is set and the round is redone on the 64-bit pipeline (its own exact draws).
-// reliability <= 0 always drops, NaN never (as the f64 comparison).
-__device__ __forceinline__ bool draw_drops(uint32_t h, double reliability, bool& tie) {
-    if (!(reliability > 0.0)) return reliability <= 0.0;
-    if (reliability >= 1.0) return false;   // chance < 1
-    const uint64_t T = (uint64_t)ceil(reliability * 9007199254740992.0);
-    const uint64_t th = T >> 21;
-    const bool low = (T & 0x1FFFFFull) != 0;
-    if (low && (uint64_t)h == th) tie = true;
-    return (uint64_t)h >= th + (low ? 1u : 0u);
-}
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-struct RelayArgs {
-    uint32_t n_hosts, n_nodes;
-    uint32_t src_lo, n_src;    // source hosts of this context: [src_lo, src_lo + n_src)
-    const uint32_t* src_off;   // [n_src + 1], host src_lo + k's sends are [src_off[k], src_off[k+1])
-    const uint64_t* send_time;
-    const uint32_t* dst_host;
-    const uint32_t* payload;
-    const double* chance;
-    const uint32_t* draw_cpu;  // CPU-drawn top 32 bits of next_u64 per packet (shd_relay_flush), or null
-    const uint32_t* host_node;
-    const uint64_t* lat;
-    const float* loss;
-    const uint64_t* rng;       // host state at round start (read)
-    const uint64_t* next_id;
-    uint64_t* rng_out;         // host state after the round (written; committed on success)
-    uint64_t* next_id_out;
-    unsigned long long* counts;  // nullable
-    uint64_t round_end, sim_end, bootstrap_end;
-    uint8_t* status;
-    uint64_t* deliver;
-    uint64_t* seq;
-    uint32_t* slot;
-    uint32_t* dst_cnt;
-    unsigned long long* red;     // [0] min deliver, [1] min latency, [2] n_sent, [3] bad dst
-};
-
-__global__ __launch_bounds__(256) void relay_stamp(RelayArgs a) {
-    const uint32_t hl = blockIdx.x * 256 + threadIdx.x, h = a.src_lo + hl;
-    uint64_t my_min_d = ~0ull, my_min_l = ~0ull, my_sent = 0;
-    if (hl < a.n_src) {
-        Xoshiro r{a.rng[4 * (size_t)h], a.rng[4 * (size_t)h + 1], a.rng[4 * (size_t)h + 2],
-                  a.rng[4 * (size_t)h + 3]};
-        uint64_t id = a.next_id[h];
-        const uint32_t sn = a.host_node[h];
-        const uint32_t i1 = a.src_off[hl + 1];
-        for (uint32_t i = a.src_off[hl]; i < i1; ++i) {
-            const uint64_t now = a.send_time[i];
-            uint8_t st = kStSkipped;
-            if (now < a.sim_end) {
-                const uint32_t d = a.dst_host[i];
-                if (d >= a.n_hosts) {  // "No host ID for dest address" (worker.rs:350-355)
-                    atomicMin(&a.red[3], (unsigned long long)i);
-                    a.status[i] = kStSkipped;
-                    continue;
-                }
-                const size_t pi = (size_t)sn * a.n_nodes + a.host_node[d];
-                const double reliability = (double)one_minus(a.loss[pi]);
-                bool ge;
-                if (a.draw_cpu) {   // the top 32 bits decide exactly for a table reliability (draw_drops)
-                    bool tie = false;
-                    ge = draw_drops(a.draw_cpu[i], reliability, tie);
-                } else {
-                    ge = (a.chance ? a.chance[i] : r.gen_f64()) >= reliability;
-                }
-                const bool boot = now < a.bootstrap_end;
-                if (!boot && ge && a.payload[i] > 0) {
-                    st = kStDropped;
-                } else {
-                    const uint64_t delay = a.lat[pi];
-                    uint64_t t = now + delay;
-                    if (t < a.round_end) t = a.round_end;
-                    st = kStSent;
-                    a.deliver[i] = t;
-                    a.seq[i] = id++;
-                    a.slot[i] = atomicAdd(&a.dst_cnt[d], 1u);
-                    if (a.counts) atomicAdd(&a.counts[pi], 1ull);
-                    my_min_d = t < my_min_d ? t : my_min_d;
-                    my_min_l = delay < my_min_l ? delay : my_min_l;
-                    ++my_sent;
-                }
-            }
-            a.status[i] = st;
-        }
-        a.rng_out[4 * (size_t)h] = r.s0;
-        a.rng_out[4 * (size_t)h + 1] = r.s1;
-        a.rng_out[4 * (size_t)h + 2] = r.s2;
-        a.rng_out[4 * (size_t)h + 3] = r.s3;
-        a.next_id_out[h] = id;
-    }
-    my_min_d = wave_min_u64(my_min_d);
-    my_min_l = wave_min_u64(my_min_l);
-    for (int o = 32; o > 0; o >>= 1) my_sent += __shfl_xor(my_sent, o);
-    if ((threadIdx.x & 63) == 0) {
-        if (my_min_d != ~0ull) atomicMin(&a.red[0], (unsigned long long)my_min_d);
-        if (my_min_l != ~0ull) atomicMin(&a.red[1], (unsigned long long)my_min_l);
-        if (my_sent) atomicAdd(&a.red[2], (unsigned long long)my_sent);
-    }
-}
-
-// Per-packet source host from the grouped offsets (binary search; hosts are few per packet).
-__device__ __forceinline__ uint32_t owner_of(const uint32_t* off, uint32_t n_hosts, uint32_t i) {
-    uint32_t lo = 0, hi = n_hosts;  // find h with off[h] <= i < off[h+1]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void relay_scatter(
-    uint64_t n, uint32_t n_src, uint32_t src_lo, const uint32_t* __restrict__ src_off,
-    const uint8_t* __restrict__ status, const uint32_t* __restrict__ dst_host,
-    const uint32_t* __restrict__ slot, const uint64_t* __restrict__ deliver,
-    const uint64_t* __restrict__ seq, const uint32_t* __restrict__ ev_off,
-    uint64_t* __restrict__ ev_deliver, uint32_t* __restrict__ ev_src, uint64_t* __restrict__ ev_seq,
-    uint32_t* __restrict__ ev_pkt) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || status[i] != kStSent) return;
-    const uint32_t pos = ev_off[dst_host[i]] + slot[i];
-    ev_deliver[pos] = deliver[i];
-    ev_src[pos] = src_lo + owner_of(src_off, n_src, (uint32_t)i);
-    ev_seq[pos] = seq[i];
-    ev_pkt[pos] = (uint32_t)i;
-}
-
-// Sort one destination's bucket by (deliver, src, seq) -- bitonic network in LDS.
-constexpr uint32_t kV1Cap = 1024;
-
-struct EvKey {
-    uint64_t t;
-    uint64_t sq;   // seq
-    uint32_t src;
-    uint32_t pkt;
-};
-__device__ __forceinline__ bool ev_less(const EvKey& a, const EvKey& b) {
-    if (a.t != b.t) return a.t < b.t;
-    if (a.src != b.src) return a.src < b.src;
-    return a.sq < b.sq;
-}
-
-__global__ __launch_bounds__(256) void segment_sort(
-    uint32_t n_hosts, const uint32_t* __restrict__ ev_off, uint64_t* __restrict__ ev_deliver,
-    uint32_t* __restrict__ ev_src, uint64_t* __restrict__ ev_seq, uint32_t* __restrict__ ev_pkt,
-    uint32_t* __restrict__ big) {
-    __shared__ EvKey s[kV1Cap];
-    const uint32_t d = blockIdx.x;
-    const uint32_t b = ev_off[d], n = ev_off[d + 1] - b;
-    if (n <= 1) return;
-    if (n > kV1Cap) {
-        if (threadIdx.x == 0) big[atomicAdd(&big[0], 1u) + 1] = d;
-        return;
-    }
-    uint32_t P = 1;
-    while (P < n) P <<= 1;
-    for (uint32_t i = threadIdx.x; i < P; i += 256) {
-        if (i < n)
-            s[i] = EvKey{ev_deliver[b + i], ev_seq[b + i], ev_src[b + i], ev_pkt[b + i]};
-        else
-            s[i] = EvKey{~0ull, ~0ull, ~0u, ~0u};
-    }
-    __syncthreads();
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < P; i += 256) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const bool up = (i & k) == 0;
-                    EvKey x = s[i], y = s[l];
-                    if (ev_less(y, x) == up) {
-                        s[i] = y;
-                        s[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < n; i += 256) {
-        const EvKey e = s[i];
-        ev_deliver[b + i] = e.t;
-        ev_src[b + i] = e.src;
-        ev_seq[b + i] = e.sq;
-        ev_pkt[b + i] = e.pkt;
-    }
-}
-
-// Oversized buckets (> kV1Cap events for one destination in one round): bottom-up merge
-// sort of that bucket by one workgroup through a global scratch area.
-__global__ __launch_bounds__(256) void segment_sort_big(
-    const uint32_t* __restrict__ big, const uint32_t* __restrict__ ev_off,
-    uint64_t* __restrict__ ev_deliver, uint32_t* __restrict__ ev_src, uint64_t* __restrict__ ev_seq,
-    uint32_t* __restrict__ ev_pkt, EvKey* __restrict__ tmp) {
-    const uint32_t d = big[1 + blockIdx.x];
-    const uint32_t b = ev_off[d], n = ev_off[d + 1] - b;
-    EvKey* A = tmp + b;  // this bucket's slice of the scratch (one EvKey per event)
-    for (uint32_t i = threadIdx.x; i < n; i += 256)
-        A[i] = EvKey{ev_deliver[b + i], ev_seq[b + i], ev_src[b + i], ev_pkt[b + i]};
-    __syncthreads();
-    // merge passes of run width w; each element finds its output rank by binary search in
-    // the sibling run (keys are unique, so ranks never collide)
-    for (uint32_t w = 1; w < n; w <<= 1) {
-        // merge runs [i, i+w) and [i+w, i+2w) into ev_* arrays, then copy back
-        for (uint32_t o = threadIdx.x; o < n; o += 256) {
-            const uint32_t run = o / (2 * w), lo = run * 2 * w;
-            const uint32_t mid = min(lo + w, n), hi = min(lo + 2 * w, n);
-            // rank of element o within the merged output: binary search in the other run
-            const EvKey x = A[o];
-            uint32_t rank;
-            if (o < mid) {
-                uint32_t l = mid, h = hi;  // count of elements in right run strictly less
-                while (l < h) {
-                    const uint32_t m = (l + h) >> 1;
-                    if (ev_less(A[m], x)) l = m + 1; else h = m;
-                }
-                rank = (o - lo) + (l - mid);
-            } else {
-                uint32_t l = lo, h = mid;  // count of elements in left run <= x (keys unique)
-                while (l < h) {
-                    const uint32_t m = (l + h) >> 1;
-                    if (ev_less(x, A[m])) h = m; else l = m + 1;
-                }
-                rank = (o - mid) + (l - lo);
-            }
-            const uint32_t dst = b + lo + rank;
-            ev_deliver[dst] = x.t;
-            ev_src[dst] = x.src;
-            ev_seq[dst] = x.sq;
-            ev_pkt[dst] = x.pkt;
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < n; i += 256)
-            A[i] = EvKey{ev_deliver[b + i], ev_seq[b + i], ev_src[b + i], ev_pkt[b + i]};
-        __syncthreads();
-    }
-}
 
 // ==========================================================================================
 // Narrow pipeline (every path latency < 2^32 ns and every deliver - round_end < 2^32): 16-byte
@@ -322,43 +27,6 @@ __global__ __launch_bounds__(256) void segment_sort_big(
 //                       (deliver offset << 32 | position in the run); ties on the deliver time
 //                       fall back to run order = (src host, event id) order
 // ==========================================================================================
-struct RelayArgs3 {
-    uint32_t n_hosts, n_nodes;
-    uint32_t src_lo, n_src;    // source hosts of this context: [src_lo, src_lo + n_src)
-    const uint32_t* src_off;   // [n_src + 1], indexed by host - src_lo
-    const uint64_t* send_time;
-    const uint32_t* dst_host;
-    const uint32_t* payload;
-    const double* chance;
-    uint32_t keep_rng;         // 1: the draws came from the CPU (shd_relay_flush): device streams untouched
-    const uint32_t* host_node;
-    const uint32_t* order;     // the n_src source host ids sorted by host_node (workgroup -> hosts)
-    const uint2* path;         // {latency ns (u32), packet loss bits} per node pair
-    const uint64_t* rng;
-    const uint64_t* next_id;
-    uint64_t* rng_out;
-    uint64_t* next_id_out;
-    unsigned long long* counts;
-    uint64_t round_end, sim_end, bootstrap_end;
-    uint32_t abs_seq;    // 1: every event id of the round fits 32 bits -> records hold absolute ids
-    uint8_t* status;
-    uint4* rec;          // per packet (valid when SENT)
-    uint32_t* key;       // per packet: destination host if SENT, else n_hosts (sorts last)
-    unsigned long long* red;   // [0] min deliver [1] min latency [2] n_sent [3] bad dst [4] wide
-                               // [5] send-order violation [6] v7 bin overflow
-    // v7 (destination-bin placement): the records of bin b written by stamp workgroup g start at
-    // bin_base[b] + seg_pre[g * n_bins + b]
-    const uint32_t* bin_base;
-    const uint32_t* seg_pre;
-    uint32_t n_bins;
-    uint32_t gs;         // hosts per group of relay_stamp_v6 / relay_bin_hist (<= kS5Hosts)
-    // v7 under a communicator (relay_round_sharded_v7): every rank's destinations [r * sh_per,
-    // ...) start a fresh bin, so rank r's bins are [r * sh_bpr, ...) and the records bound for it
-    // one contiguous slice; sh_mul = ceil(2^40 / sh_per).  sh_per = 0: bins of consecutive hosts.
-    uint32_t sh_per, sh_bpr;
-    uint64_t sh_mul;
-};
-
 #ifndef SHD_DRAW_SLICE
 #define SHD_DRAW_SLICE 16
 #endif
@@ -1164,201 +832,6 @@ __global__ __launch_bounds__(256) void pack_path(const uint64_t* __restrict__ la
     if (i < nn) out[i] = make_uint2((uint32_t)lat[i], __float_as_uint(loss[i]));
 }
 
-// ev_off[d] = first position of destination d in the sorted keys (lower bound), d in [0, H]
-__global__ __launch_bounds__(256) void bucket_offsets(const uint32_t* __restrict__ key, uint64_t n,
-                                                      uint32_t n_hosts, uint32_t* __restrict__ ev_off) {
-    const uint32_t d = blockIdx.x * 256 + threadIdx.x;
-    if (d > n_hosts) return;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t m = (lo + hi) >> 1;
-        if (key[m] < d) lo = m + 1; else hi = m;
-    }
-    ev_off[d] = (uint32_t)lo;
-}
-
-__device__ __forceinline__ bool rec_less(const uint4& a, const uint4& b) {
-    if (a.x != b.x) return a.x < b.x;     // deliver offset
-    if (a.y != b.y) return a.y < b.y;     // src host
-    return a.z < b.z;                     // event id offset
-}
-
-constexpr uint32_t kWaveSeg = 256;
-
-// Sort one destination run held in LDS (xs[0..n), n <= kWaveSeg) by one wave; writes the sorted
-// order as LDS positions pm[e] = base + position.  32-bit keys ((offset - min) << PB | position)
-// when the run's deliver offsets leave room for PB position bits, else 64-bit keys.
-template <int NPL, int PB>
-__device__ __forceinline__ void wave_sort_perm(uint32_t n, uint32_t lane, const uint4* xs,
-                                               uint32_t lo, uint32_t span, uint16_t* pm,
-                                               uint32_t base) {
-    if (span < (1u << (32 - PB)) - 1u) {
-        uint32_t k[NPL];
-#pragma unroll
-        for (int c = 0; c < NPL; ++c) {
-            const uint32_t e = lane + 64u * c;
-            k[c] = e < n ? ((xs[e].x - lo) << PB) | e : ~0u;
-        }
-        wave_bitonic32<NPL>(k, lane);
-#pragma unroll
-        for (int c = 0; c < NPL; ++c) {
-            const uint32_t e = lane + 64u * c;
-            if (e < n) pm[e] = (uint16_t)(base + (k[c] & ((1u << PB) - 1u)));
-        }
-    } else {
-        uint64_t k[NPL];
-#pragma unroll
-        for (int c = 0; c < NPL; ++c) {
-            const uint32_t e = lane + 64u * c;
-            k[c] = e < n ? (((uint64_t)xs[e].x << 32) | e) : ~0ull;
-        }
-        wave_bitonic<NPL>(k, lane);
-#pragma unroll
-        for (int c = 0; c < NPL; ++c) {
-            const uint32_t e = lane + 64u * c;
-            if (e < n) pm[e] = (uint16_t)(base + (uint32_t)k[c]);
-        }
-    }
-}
-
-__device__ __forceinline__ void wave_sort_run(uint32_t n, uint32_t lane, const uint4* xs,
-                                              uint16_t* pm, uint32_t base) {
-    uint32_t lo = ~0u, hi = 0;
-    for (uint32_t e = lane; e < n; e += 64) {
-        lo = min(lo, xs[e].x);
-        hi = max(hi, xs[e].x);
-    }
-    lo = wave_min_u32(lo, lane);
-    const uint32_t span = wave_max_u32(hi, lane) - lo;
-    if (n <= 64) wave_sort_perm<1, 6>(n, lane, xs, lo, span, pm, base);
-    else if (n <= 128) wave_sort_perm<2, 7>(n, lane, xs, lo, span, pm, base);
-    else wave_sort_perm<4, 8>(n, lane, xs, lo, span, pm, base);
-}
-
-// K4: a workgroup owns kSegDst consecutive destinations; their runs are one contiguous range of
-// the sorted records, so it is loaded and stored in bulk (coalesced) while each wave sorts whole
-// runs in LDS.  Runs longer than kWaveSeg go to the merge kernel; a range larger than the LDS
-// stage (only with such runs) is handled run by run.
-constexpr uint32_t kSegDst = 8;
-constexpr uint32_t kRunCap = 1536;
-
-__global__ __launch_bounds__(256) void segment_sort_v5(
-    uint32_t n_hosts, const uint32_t* __restrict__ ev_off, const uint4* __restrict__ brec,
-    uint64_t round_end, const uint64_t* __restrict__ seq_base, uint64_t* __restrict__ ev_deliver,
-    uint32_t* __restrict__ ev_src, uint64_t* __restrict__ ev_seq, uint32_t* __restrict__ ev_pkt,
-    uint32_t* __restrict__ big) {
-    __shared__ uint4 x[kRunCap];
-    __shared__ uint16_t pm[kRunCap];
-    __shared__ uint32_t off[kSegDst + 1];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t d0 = blockIdx.x * kSegDst;
-    const uint32_t nd = min(kSegDst, n_hosts - d0);
-    if (tid <= nd) off[tid] = ev_off[d0 + tid];
-    __syncthreads();
-    const uint32_t B = off[0], N = off[nd] - B;
-    if (N > kRunCap) {   // run by run through a per-wave stage
-        uint4* xw = x + w * kWaveSeg;
-        uint16_t* pw = pm + w * kWaveSeg;
-        for (uint32_t dl = w; dl < nd; dl += 4) {
-            const uint32_t b = off[dl], n = off[dl + 1] - b;
-            if (n == 0) continue;
-            if (n > kWaveSeg) {
-                if (lane == 0) big[atomicAdd(&big[0], 1u) + 1] = d0 + dl;
-                continue;
-            }
-            for (uint32_t e = lane; e < n; e += 64) xw[e] = brec[b + e];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            wave_sort_run(n, lane, xw, pw, 0);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (uint32_t e = lane; e < n; e += 64) {
-                const uint4 r = xw[pw[e]];
-                ev_deliver[b + e] = round_end + r.x;
-                ev_src[b + e] = r.y;
-                ev_seq[b + e] = seq_base ? seq_base[r.y] + r.z : r.z;
-                ev_pkt[b + e] = r.w;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        return;
-    }
-    for (uint32_t i = tid; i < N; i += 256) x[i] = brec[B + i];
-    __syncthreads();
-    for (uint32_t dl = w; dl < nd; dl += 4) {
-        const uint32_t b = off[dl] - B, n = off[dl + 1] - off[dl];
-        if (n == 0) continue;
-        if (n > kWaveSeg) {   // the merge kernel writes this run; the bulk store skips it
-            if (lane == 0) big[atomicAdd(&big[0], 1u) + 1] = d0 + dl;
-            for (uint32_t e = lane; e < n; e += 64) pm[b + e] = 0xFFFFu;
-            continue;
-        }
-        wave_sort_run(n, lane, x + b, pm + b, b);
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < N; i += 256) {
-        const uint32_t p = pm[i];
-        if (p == 0xFFFFu) continue;
-        const uint4 r = x[p];
-        ev_deliver[B + i] = round_end + r.x;
-        ev_src[B + i] = r.y;
-        ev_seq[B + i] = seq_base ? seq_base[r.y] + r.z : r.z;
-        ev_pkt[B + i] = r.w;
-    }
-}
-
-// Runs longer than kWaveSeg: bottom-up merge passes by one workgroup in a
-// global scratch copy of the bucket (rank by binary search in the sibling run; keys unique).
-__global__ __launch_bounds__(256) void segment_sort_v2_big(
-    const uint32_t* __restrict__ big, const uint32_t* __restrict__ ev_off, uint4* __restrict__ brec,
-    uint4* __restrict__ tmp, uint64_t round_end, const uint64_t* __restrict__ seq_base,
-    uint64_t* __restrict__ ev_deliver, uint32_t* __restrict__ ev_src, uint64_t* __restrict__ ev_seq,
-    uint32_t* __restrict__ ev_pkt) {
-    for (uint32_t bi = blockIdx.x; bi < big[0]; bi += gridDim.x) {
-        const uint32_t d = big[1 + bi];
-        const uint32_t b = ev_off[d], n = ev_off[d + 1] - b;
-        uint4* A = brec + b;
-        uint4* T = tmp + b;
-        for (uint32_t w = 1; w < n; w <<= 1) {
-            for (uint32_t o = threadIdx.x; o < n; o += 256) {
-                const uint32_t lo = (o / (2 * w)) * 2 * w;
-                const uint32_t mid = min(lo + w, n), hi = min(lo + 2 * w, n);
-                const uint4 xv = A[o];
-                uint32_t rank;
-                if (o < mid) {
-                    uint32_t l = mid, h = hi;
-                    while (l < h) {
-                        const uint32_t m = (l + h) >> 1;
-                        if (rec_less(A[m], xv)) l = m + 1; else h = m;
-                    }
-                    rank = (o - lo) + (l - mid);
-                } else {
-                    uint32_t l = lo, h = mid;
-                    while (l < h) {
-                        const uint32_t m = (l + h) >> 1;
-                        if (rec_less(xv, A[m])) h = m; else l = m + 1;
-                    }
-                    rank = (o - mid) + (l - lo);
-                }
-                T[lo + rank] = xv;
-            }
-            __syncthreads();
-            for (uint32_t o = threadIdx.x; o < n; o += 256) A[o] = T[o];
-            __syncthreads();
-        }
-        for (uint32_t i = threadIdx.x; i < n; i += 256) {
-            const uint4 e = A[i];
-            ev_deliver[b + i] = round_end + e.x;
-            ev_src[b + i] = e.y;
-            ev_seq[b + i] = seq_base ? seq_base[e.y] + e.z : e.z;
-            ev_pkt[b + i] = e.w;
-        }
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // Multi-GPU receive side: k-way merge of per-sender runs.  The input is n_runs chunks laid end
 // to end; chunk r holds its events grouped by destination (local offsets off[r][0..n_dst]) and
@@ -1382,125 +855,6 @@ __global__ __launch_bounds__(256) void merge_offsets(uint32_t n_runs, uint32_t n
     for (uint32_t r = 0; r < n_runs; ++r) t += off[(size_t)r * (n_dst + 1) + d] - off[(size_t)r * (n_dst + 1)];
     out_off[d] = t;
 }
-
-__global__ void max_u64_kernel(const uint64_t* __restrict__ d, uint64_t n,
-                               unsigned long long* __restrict__ out) {
-    uint64_t m = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-        m = d[i] > m ? d[i] : m;
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = __shfl_xor(m, o);
-        m = w > m ? w : m;
-    }
-    // one atomic per workgroup: 4 waves per block on one address contend (97 us for 8 MB)
-    __shared__ uint64_t part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) m = part[w] > m ? part[w] : m;
-        atomicMax(out, (unsigned long long)m);
-    }
-}
-
-__global__ void min_u64_kernel(const uint64_t* __restrict__ d, uint64_t n,
-                               unsigned long long* __restrict__ out) {
-    uint64_t m = ~0ull;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-        m = d[i] < m ? d[i] : m;
-    m = wave_min_u64(m);
-    __shared__ uint64_t part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) m = part[w] < m ? part[w] : m;
-        atomicMin(out, (unsigned long long)m);
-    }
-}
-
-shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out) {
-    SHD_TRY(ctx->g_aux.ensure(8));
-    SHD_HIP(hipMemsetAsync(ctx->g_aux.p, 0xFF, 8, ctx->stream));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
-    min_u64_kernel<<<grid ? grid : 1, 256, 0, ctx->stream>>>(
-        d, n, reinterpret_cast<unsigned long long*>(ctx->g_aux.p));
-    SHD_HIP(hipMemcpyAsync(out, ctx->g_aux.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SHD_HIP(hipStreamSynchronize(ctx->stream));
-    return SHD_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Host side
-// ------------------------------------------------------------------------------------------
-// v1 pipeline: u64 deliver times (used when a path latency or deliver offset needs > 32 bits)
-static shd_status relay_device_v1(shd_ctx* ctx, const shd_batch* b, const shd_round* rd,
-                                  shd_relay_out* o) {
-    RelayState& R = ctx->relay;
-    hipStream_t s = ctx->stream;
-    const uint64_t n = b->n_packets;
-    const uint32_t H = R.n_hosts;
-    SHD_TRY(R.ev_key.ensure(std::max<uint64_t>(n, 1) * 8));   // deliver per packet
-    SHD_TRY(R.ev_key2.ensure(std::max<uint64_t>(n, 1) * 8));  // seq per packet
-    SHD_TRY(R.ev_val.ensure(std::max<uint64_t>(n, 1) * 4));   // slot per packet
-    unsigned long long init[8] = {~0ull, ~0ull, 0ull, ~0ull, 0ull, 0ull, 0ull, 0ull};
-    SHD_HIP(hipMemcpyAsync(R.red.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    SHD_HIP(hipMemsetAsync(R.dst_cnt.p, 0, (size_t)(H + 1) * 4, s));
-    RelayArgs a{};
-    a.n_hosts = H;
-    a.n_nodes = R.n_nodes;
-    a.src_lo = R.src_lo;
-    a.n_src = R.n_src;
-    a.src_off = b->src_off;
-    a.send_time = b->send_time;
-    a.dst_host = b->dst_host;
-    a.payload = b->payload;
-    a.chance = b->chance;
-    a.draw_cpu = R.cpu_draws ? R.draws.as<uint32_t>() : nullptr;
-    a.host_node = R.host_node.as<uint32_t>();
-    a.lat = R.own_table ? R.lat.as<uint64_t>() : ctx->t_lat.as<uint64_t>();
-    a.loss = R.own_table ? R.loss.as<float>() : ctx->t_loss.as<float>();
-    a.rng = R.rng.as<uint64_t>();
-    a.next_id = R.next_id.as<uint64_t>();
-    a.rng_out = R.rng2.as<uint64_t>();
-    a.next_id_out = R.next_id2.as<uint64_t>();
-    a.counts = R.count_on ? R.counts_round.as<unsigned long long>() : nullptr;
-    a.round_end = rd->round_end;
-    a.sim_end = rd->sim_end;
-    a.bootstrap_end = rd->bootstrap_end;
-    a.status = o->status;
-    a.deliver = R.ev_key.as<uint64_t>();
-    a.seq = R.ev_key2.as<uint64_t>();
-    a.slot = R.ev_val.as<uint32_t>();
-    a.dst_cnt = R.dst_cnt.as<uint32_t>();
-    a.red = R.red.as<unsigned long long>();
-    relay_stamp<<<div_up(std::max<uint32_t>(R.n_src, 1), 256), 256, 0, s>>>(a);
-    SHD_HIP(hipGetLastError());
-    // destination offsets: one hand-written look-back scan launch (scan.h); ev_off must be
-    // 16-byte aligned (the relay's own buffers are; a caller's device array from hipMalloc too)
-    SHD_TRY(scan_excl2(R.scan, R.dst_cnt.as<uint32_t>(), o->ev_off, nullptr, nullptr, (uint64_t)H + 1, s));
-    if (n)
-        relay_scatter<<<div_up(n, 256), 256, 0, s>>>(n, R.n_src, R.src_lo, b->src_off, o->status, b->dst_host,
-                                                     R.ev_val.as<uint32_t>(), R.ev_key.as<uint64_t>(),
-                                                     R.ev_key2.as<uint64_t>(), o->ev_off, o->ev_deliver,
-                                                     o->ev_src, o->ev_seq, o->ev_pkt);
-    SHD_TRY(R.ev_val2.ensure((size_t)(H + 2) * 4));
-    SHD_HIP(hipMemsetAsync(R.ev_val2.p, 0, 4, s));
-    segment_sort<<<H, 256, 0, s>>>(H, o->ev_off, o->ev_deliver, o->ev_src, o->ev_seq, o->ev_pkt,
-                                   R.ev_val2.as<uint32_t>());
-    SHD_HIP(hipGetLastError());
-    uint32_t n_big = 0;
-    SHD_HIP(hipMemcpyAsync(&n_big, R.ev_val2.p, 4, hipMemcpyDeviceToHost, s));
-    SHD_HIP(hipMemcpyAsync(R.red_host, R.red.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SHD_HIP(hipStreamSynchronize(s));
-    if (n_big) {
-        SHD_TRY(R.tmp.ensure(std::max<uint64_t>(n, 1) * sizeof(EvKey)));
-        segment_sort_big<<<n_big, 256, 0, s>>>(R.ev_val2.as<uint32_t>(), o->ev_off, o->ev_deliver,
-                                               o->ev_src, o->ev_seq, o->ev_pkt, R.tmp.as<EvKey>());
-        SHD_HIP(hipGetLastError());
-        SHD_HIP(hipStreamSynchronize(s));
-    }
-    return SHD_OK;
-}
-
 
 // ==========================================================================================
 // Pipeline v7: destination-bin placement instead of a radix sort.  The stamp writes every
@@ -1951,6 +1305,11 @@ __global__ __launch_bounds__(64) void xs_fin_empty(XSrc xs, uint32_t* __restrict
     }
 }
 
+// Phase pricing (tuning builds, tools/b7_phases.sh): -DSHD_B7_STOP=k makes bin_sort_v7 return after
+// phase k = 1 load, 2 look-back, 3 grouping, 4 sorts; the output is wrong, only the time is read
+#ifndef SHD_B7_STOP
+#define SHD_B7_STOP 0
+#endif
 // K4 (v7): one workgroup per bin, bins taken in ticket order so the event offsets can use a
 // decoupled look-back (publish the bin's sent count, add the predecessors' counts).  The bin's
 // records are staged in LDS, grouped by destination, each run sorted by one wave into the
@@ -1961,9 +1320,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
                                                           const uint4* __restrict__ rec,
                                                           unsigned long long* __restrict__ lb,
                                                           uint32_t* __restrict__ ev_off, V7Out o,
-                                                          const unsigned long long* __restrict__ red,
-                                                          uint32_t stop,   // tuning: stop after phase
-                                                          XSrc xs) {
+                                                          const unsigned long long* __restrict__ red, XSrc xs) {
     __shared__ uint4 x[kB7Cap];
     __shared__ uint16_t ls[kB7Cap], pm[kB7Cap];
     __shared__ uint32_t s_cnt[kBinDst], s_off[kBinDst + 1], s_cur[kBinDst], s_bin, s_excl;
@@ -1980,7 +1337,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
     // them in registers, so no wave waits at a barrier for another's loads before its record
     // loads (measured the same as a wave-0 table in LDS behind a barrier: the X form's extra
     // ~25 us over bin_sort_v7<false> at world size 1 is its look-back phase, +13 us, and the
-    // loads, +6 us; tools/r06_b7x_phases.sh)
+    // loads, +6 us; priced with SHD_B7_STOP builds)
     uint32_t x_at = 0, x_pre = 0, x_pb = 0;
     if constexpr (X) {
         uint32_t c = 0;
@@ -2039,7 +1396,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
         }
     }
     __syncthreads();
-    if (stop == 1) return;
+    if (SHD_B7_STOP == 1) return;
     if (w == 0) {
         const uint32_t c = lane < kBinDst ? s_cnt[lane] : 0u;
         uint32_t incl = c;
@@ -2085,7 +1442,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
         ev_off[n_hosts] = excl + S;
         if constexpr (X) ev_off[n_hosts + 1] = xs_status(xs);   // (read back with the count)
     }
-    if (stop == 2) return;
+    if (SHD_B7_STOP == 2) return;
     for (uint32_t i = tid; i < N; i += kB7Threads) {
         const uint32_t y = x[i].y;
         if (((y >> 24) & 3u) == kStSent) {
@@ -2094,7 +1451,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
         }
     }
     __syncthreads();
-    if (stop == 3) return;
+    if (SHD_B7_STOP == 3) return;
     for (uint32_t dl = w; dl < kBinDst; dl += kB7Threads / 64) {
         const uint32_t b = s_off[dl], n = s_off[dl + 1] - b;
         if (n == 0) continue;
@@ -2114,7 +1471,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
         }
     }
     __syncthreads();
-    if (stop == 4) return;
+    if (SHD_B7_STOP == 4) return;
     for (uint32_t p = tid; p < S; p += kB7Threads) {
         uint4 r = x[pm[p]];
         if constexpr (X) {
@@ -2125,17 +1482,7 @@ __global__ __launch_bounds__(kB7Threads) void bin_sort_v7(uint32_t n_hosts, uint
     }
 }
 
-// Narrow pipeline: K1 stamp, K2 radix sort by destination, K3 offsets, K4 per-run sort; one
-// host sync (for the round reductions).
-// the round's reductions: [0] min deliver, [1] min latency, [2] sent, [3] first bad index,
-// [4] wide offset, [5] send-order violation; plus the big-run counter of K4
-__global__ __launch_bounds__(64) void red_init(unsigned long long* __restrict__ red, uint32_t* __restrict__ n_big) {
-    const uint32_t t = threadIdx.x;
-    if (t < 8) red[t] = (t <= 1 || t == 3) ? ~0ull : 0ull;
-    if (t == 0) *n_big = 0;
-}
-
-static RelayArgs3 relay_args3(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o) {
+RelayArgs3 relay_args3(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o) {
     RelayState& R = ctx->relay;
     const uint64_t n = b->n_packets;
     const uint32_t H = R.n_hosts;
@@ -2172,24 +1519,15 @@ static RelayArgs3 relay_args3(shd_ctx* ctx, const shd_batch* b, const shd_round*
     return a;
 }
 
-static shd_status relay_device_v3(shd_ctx* ctx, const shd_batch* b, const shd_round* rd,
-                                  shd_relay_out* o) {
+void relay_launch_draws(shd_ctx* ctx, const RelayArgs3& a) {
+    RelayState& R = ctx->relay;
+    if (a.chance || R.cpu_draws || !R.n_src) return;   // (shd_relay_flush filled the draws from the CPU's)
+    relay_draws<<<div_up(R.n_src, 64 * kK0Waves), 64 * kK0Waves, 0, ctx->stream>>>(a, R.draws.as<uint32_t>());
+}
+
+void relay_launch_stamp(shd_ctx* ctx, const RelayArgs3& a) {
     RelayState& R = ctx->relay;
     hipStream_t s = ctx->stream;
-    const uint64_t n = b->n_packets;
-    const uint32_t H = R.n_hosts;
-    const size_t nn = std::max<uint64_t>(n, 1);
-    SHD_TRY(R.rec.ensure(nn * 16));
-    SHD_TRY(R.brec.ensure(nn * 16));
-    SHD_TRY(R.ev_val.ensure(nn * 4));    // keys
-    SHD_TRY(R.ev_key.ensure(nn * 4));    // keys (second buffer)
-    SHD_TRY(R.ev_val2.ensure((size_t)(H + 2) * 4));
-    SHD_TRY(R.draws.ensure(nn * 4));
-    red_init<<<1, 64, 0, s>>>(R.red.as<unsigned long long>(), R.ev_val2.as<uint32_t>());
-    RelayArgs3 a = relay_args3(ctx, b, rd, o);
-    const uint64_t* seq_base = a.abs_seq ? nullptr : R.next_id.as<uint64_t>();
-    if (!b->chance && !R.cpu_draws && R.n_src)   // K0: the per-host generator streams
-        relay_draws<<<div_up(R.n_src, 64 * kK0Waves), 64 * kK0Waves, 0, s>>>(a, R.draws.as<uint32_t>());
     if (R.n_src == 0) {
     } else if (R.hn_bits) {   // host -> node map fits the LDS: persistent stamp, no node gathers
         const uint32_t groups = div_up(R.n_src, kS5Hosts);
@@ -2200,29 +1538,15 @@ static shd_status relay_device_v3(shd_ctx* ctx, const shd_batch* b, const shd_ro
         (a.chance ? relay_stamp_v5<true> : relay_stamp_v5<false>)<<<div_up(R.n_src, kS5Hosts), 256, 0, s>>>(
             a, R.draws.as<uint32_t>());
     }
+}
+
+shd_status relay_read_red(shd_ctx* ctx) {
+    RelayState& R = ctx->relay;
     SHD_HIP(hipGetLastError());
-    // stable LSD radix sort of the records by destination (keys <= H), hand-written (scan.h)
-    uint32_t bits = 1;
-    while (bits < 32 && (H >> bits) != 0) ++bits;
-    bool first = true;
-    SHD_TRY(radix_sort_pairs(R.rs_counts, R.rs_scan, R.ev_val.as<uint32_t>(), R.rec.as<uint4>(),
-                             R.ev_key.as<uint32_t>(), R.brec.as<uint4>(), n, bits, &first, s));
-    uint4* sorted = first ? R.rec.as<uint4>() : R.brec.as<uint4>();
-    uint4* spare = first ? R.brec.as<uint4>() : R.rec.as<uint4>();
-    const uint32_t* skeys = first ? R.ev_val.as<uint32_t>() : R.ev_key.as<uint32_t>();
-    bucket_offsets<<<div_up((uint64_t)H + 1, 256), 256, 0, s>>>(skeys, n, H, o->ev_off);
-    segment_sort_v5<<<div_up(H, kSegDst), 256, 0, s>>>(
-        H, o->ev_off, sorted, rd->round_end, seq_base, o->ev_deliver, o->ev_src,
-        o->ev_seq, o->ev_pkt, R.ev_val2.as<uint32_t>());
-    segment_sort_v2_big<<<64, 256, 0, s>>>(R.ev_val2.as<uint32_t>(), o->ev_off, sorted,
-                                           spare, rd->round_end, seq_base,
-                                           o->ev_deliver, o->ev_src, o->ev_seq, o->ev_pkt);
-    SHD_HIP(hipGetLastError());
-    SHD_TRY(readback(ctx, s, 8, R.red.p, 8 * sizeof(unsigned long long)));
+    SHD_TRY(readback(ctx, ctx->stream, 8, R.red.p, 8 * sizeof(unsigned long long)));
     std::memcpy(R.red_host, ctx->h_pin + 8, sizeof(R.red_host));
     return SHD_OK;
 }
-
 
 // v7 eligibility: narrow table, LDS host map, src ids and packet indices within the record /
 // key fields, and the stamp's LDS (map + slot counters) within the CU's 160 KB
@@ -2312,22 +1636,10 @@ static shd_status relay_device_v7(shd_ctx* ctx, const shd_batch* b, const shd_ro
     a.n_bins = n_bins;
     uint32_t* seg = R.bin_cnt.as<uint32_t>() + (size_t)G * kHistSplit * n_bins;
     a.seg_pre = seg;
-    // (side-stream form: K0 goes first -- with the draws kept as 4 bytes and the histogram at 30
-    // us, K0 plus the stream join (~12 us from its end to the stamp's start) was the longer of the
-    // two chains, so its fork is issued before anything else.  The fork event follows the
-    // caller's work on the stream, e.g. the kernels that wrote the batch.)
-    const bool k0 = !b->chance && !R.cpu_draws;   // (shd_relay_flush filled the draws from the CPU's)
-    // K0 in line before the histogram (default, round 5): K0 30 us + histogram 21 us back to back
-    // beat K0 beside the histogram (39 ‖ 41 us, each slowed by the other taking wave slots) plus
-    // the fork / join events: C5 round 0.467-0.476 -> 0.457 ms.  SHD_RELAY_K0_INLINE=0: the side stream.
-    const bool k0_inline = k0 && ctx->knobs.get(K_RELAY_K0_INLINE, 1) != 0;
-    if (k0_inline) {
-        relay_draws<<<div_up(R.n_src, 64 * kK0Waves), 64 * kK0Waves, 0, s>>>(a, R.draws.as<uint32_t>());
-    } else if (k0) {   // K0: the per-host generator streams, on the side stream next to the bins
-        SHD_HIP(hipEventRecord(ctx->sev[0], s));
-        SHD_HIP(hipStreamWaitEvent(ctx->side, ctx->sev[0], 0));
-        relay_draws<<<div_up(R.n_src, 64 * kK0Waves), 64 * kK0Waves, 0, ctx->side>>>(a, R.draws.as<uint32_t>());
-    }
+    // K0 in line before the histogram (round 5): K0 30 us + histogram 21 us back to back beat K0
+    // beside the histogram on a side stream (39 ‖ 41 us, each slowed by the other taking wave
+    // slots) plus the fork / join events: C5 round 0.467-0.476 -> 0.457 ms
+    relay_launch_draws(ctx, a);
     // the histogram's first block also resets the round's reductions (red_init's job: one
     // launch less; only the scans and the stamp read them, all after the histogram)
     // (SHD_HIST_SCALAR=1, tuning A/B: the flattened-position form)
@@ -2336,7 +1648,6 @@ static shd_status relay_device_v7(shd_ctx* ctx, const shd_batch* b, const shd_ro
                                                                              R.bin_cnt.as<uint32_t>());
     else
         relay_bin_hist<<<G * kHistSplit, 256, (size_t)n_bins * 4, s>>>(a, G, R.bin_cnt.as<uint32_t>());
-    if (k0 && !k0_inline) SHD_HIP(hipEventRecord(ctx->sev[1], ctx->side));   // after the histogram's launch
     if (ctx->knobs.get(K_RELAY_SCAN2, 0) != 0 || div_up(n_bins, 64) > 128) {   // (A/B: two launches)
         bin_col_scan<<<div_up(n_bins, 64), 1024, 0, s>>>(G, n_bins, R.bin_cnt.as<uint32_t>(), seg, tot, a.red);
         bin_base_scan<<<1, 1024, 0, s>>>(n_bins, tot, R.bin_base.as<uint32_t>(), R.bin_lb.as<unsigned long long>(), a.red);
@@ -2356,7 +1667,6 @@ static shd_status relay_device_v7(shd_ctx* ctx, const shd_batch* b, const shd_ro
                                                        R.bin_base.as<uint32_t>(), R.bin_lb.as<unsigned long long>(),
                                                        SS.state.as<unsigned long long>(), SS.epoch);
     }
-    if (k0 && !k0_inline) SHD_HIP(hipStreamWaitEvent(s, ctx->sev[1], 0));
     // (no LDS host map -- e.g. C5b's 50k nodes -- : the stamp gathers the destinations' nodes)
     auto* stamp = R.hn_bits ? (a.chance ? &relay_stamp_v6<true, true> : &relay_stamp_v6<true, false>)
                             : (a.chance ? &relay_stamp_v6<true, true, false> : &relay_stamp_v6<true, false, false>);
@@ -2374,14 +1684,10 @@ static shd_status relay_device_v7(shd_ctx* ctx, const shd_batch* b, const shd_ro
         vo.fl_b12 = R.fl_b12;
         R.fl_direct = true;
     }
-    const uint32_t stop = ctx->knobs.get(K_B7_STOP, 0);   // tuning only: partial K4 (wrong output)
     bin_sort_v7<false><<<n_bins, kB7Threads, 0, s>>>(H, n_bins, R.bin_base.as<uint32_t>(), R.rec.as<uint4>(),
                                                     R.bin_lb.as<unsigned long long>(), o->ev_off, vo, a.red,
-                                                    stop, XSrc{});
-    SHD_HIP(hipGetLastError());
-    SHD_TRY(readback(ctx, s, 8, R.red.p, 8 * sizeof(unsigned long long)));
-    std::memcpy(R.red_host, ctx->h_pin + 8, sizeof(R.red_host));
-    return SHD_OK;
+                                                    XSrc{});
+    return relay_read_red(ctx);
 }
 
 // One round: the new host state (RNG streams, event ids) is written to the second buffer and
@@ -2396,45 +1702,42 @@ __global__ __launch_bounds__(256) void counts_commit(unsigned long long* __restr
     }
 }
 
-// The round's pipelines and checks; nothing of the hosts' state is committed yet.
+// The round's pipelines and checks; nothing of the hosts' state is committed yet.  A ladder: the
+// bins (7), else the radix sort (3) when a bin overflowed or the bins do not apply, else the
+// 64-bit records (1) when the table or a deliver offset of this round is wide.
 static shd_status relay_run(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o) {
     RelayState& R = ctx->relay;
     const uint32_t H = R.n_hosts;
     const uint64_t nn = (uint64_t)R.n_nodes * R.n_nodes;
     SHD_TRY(R.red.ensure(64));
     SHD_TRY(R.dst_cnt.ensure((size_t)(H + 1) * 4));
-    // every pipeline attempt counts into a zeroed per-round buffer; only the committed attempt
-    // reaches the counters (a rerun or a failed round must not count)
-    auto zero_counts = [&]() -> shd_status {
+    if (R.count_on) SHD_TRY(R.counts_round.ensure(nn * 8));
+    // every rung counts into a zeroed per-round buffer; only the committed attempt reaches the
+    // counters (a rerun or a failed round must not count)
+    auto rung = [&](int pipe) -> shd_status {
         if (R.count_on) SHD_HIP(hipMemsetAsync(R.counts_round.p, 0, nn * 8, ctx->stream));
+        R.last_pipe = pipe;
         return SHD_OK;
     };
-    if (R.count_on) SHD_TRY(R.counts_round.ensure(nn * 8));
-    bool v2 = R.table_narrow && !R.force_v1;
-    R.last_pipe = 1;
-    if (v2) {
-        bool done = false;
-        if (relay_v7_ok(ctx, b->n_packets, div_up(H, kBinDst))) {
-            SHD_TRY(zero_counts());
-            SHD_TRY(relay_device_v7(ctx, b, rd, o));
-            done = !R.red_host[6];   // else a bin overflowed: redo with the radix pipeline
-            R.last_pipe = 7;
-        }
-        if (!done) {
-            SHD_TRY(zero_counts());
-            SHD_TRY(relay_device_v3(ctx, b, rd, o));
-            R.last_pipe = 3;
-        }
-        if (R.red_host[4]) v2 = false;   // a deliver offset needs 64 bits: redo with v1
+    bool narrow = R.table_narrow && !R.force_v1;
+    bool sorted = false;
+    if (narrow && relay_v7_ok(ctx, b->n_packets, div_up(H, kBinDst))) {
+        SHD_TRY(rung(7));
+        SHD_TRY(relay_device_v7(ctx, b, rd, o));
+        sorted = !R.red_host[6];   // else a bin overflowed: redo with the radix pipeline
     }
-    if (!v2) R.last_pipe = 1;
-    if (!v2) {
-        SHD_TRY(zero_counts());
+    if (narrow && !sorted) {
+        SHD_TRY(rung(3));
+        SHD_TRY(relay_device_v3(ctx, b, rd, o));
+    }
+    if (narrow && R.red_host[4]) narrow = false;   // a deliver offset needs 64 bits: redo with v1
+    if (!narrow) {
+        SHD_TRY(rung(1));
         SHD_TRY(relay_device_v1(ctx, b, rd, o));
     }
     if (R.red_host[3] != ~0ull) return SHD_ERR_NO_HOST;
-    if (v2 && R.red_host[5]) return SHD_ERR_INVALID;   // a host's send times went backwards
-    R.last_v2 = v2;
+    if (narrow && R.red_host[5]) return SHD_ERR_INVALID;   // a host's send times went backwards
+    R.last_v2 = narrow;
     return SHD_OK;
 }
 
@@ -2539,71 +1842,12 @@ __global__ __launch_bounds__(256) void shard_offsets(uint32_t world, uint32_t H,
     if (i <= hi - lo) stage[lo + r + i] = ev_off[lo + i] - ev_off[lo];
 }
 
-// thread per received event: its rank among its destination's events of all runs
-__global__ __launch_bounds__(256) void merge_runs24(uint32_t n_runs, uint32_t n_dst,
-                                                    const uint32_t* __restrict__ base,   // [n_runs + 1]
-                                                    const uint32_t* __restrict__ off,    // [n_runs][n_dst + 1]
-                                                    const Ev24* __restrict__ in,
-                                                    const uint32_t* __restrict__ out_off,
-                                                    uint64_t* __restrict__ out_t, uint32_t* __restrict__ out_s,
-                                                    uint64_t* __restrict__ out_q, uint32_t* __restrict__ out_p) {
-    // The event's destination d: a run's events are in destination order and a block takes 256
-    // consecutive events, so threads 0 and 1 search the whole offset row for the block's first
-    // and last event (when both lie in one run) and every thread then searches only between the
-    // two (~3 destinations on C5) -- instead of 17 dependent loads over 100k offsets per event.
-    __shared__ uint32_t s_d[2];
-    const uint32_t total = base[n_runs];
-    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t e0 = blockIdx.x * 256, e1 = min(e0 + 255, total - 1);
-    auto run_of = [&](uint32_t x) {
-        uint32_t r = 0;
-        while (r + 1 < n_runs && base[r + 1] <= x) ++r;
-        return r;
-    };
-    auto dst_of = [&](const uint32_t* o, uint32_t le, uint32_t lo, uint32_t hi) {   // o[d] <= le < o[d+1]
-        while (hi - lo > 1) {
-            const uint32_t m = (lo + hi) >> 1;
-            if (o[m] <= le) lo = m; else hi = m;
-        }
-        return lo;
-    };
-    const uint32_t rb0 = run_of(e0), rb1 = run_of(e1);
-    const uint32_t* ob = off + (size_t)rb0 * (n_dst + 1);
-    if (rb0 == rb1 && threadIdx.x < 2) s_d[threadIdx.x] = dst_of(ob, (threadIdx.x ? e1 : e0) - base[rb0], 0, n_dst);
-    __syncthreads();
-    if (e >= total) return;   // no barrier follows
-    const uint32_t r = rb0 == rb1 ? rb0 : run_of(e);
-    const uint32_t le = e - base[r];
-    const uint32_t* o = off + (size_t)r * (n_dst + 1);
-    const uint32_t d = rb0 == rb1 ? dst_of(o, le, s_d[0], s_d[1] + 1) : dst_of(o, le, 0, n_dst);
-    const Ev24 x = in[e];
-    uint32_t rank = le - o[d];
-    for (uint32_t r2 = 0; r2 < n_runs; ++r2) {
-        if (r2 == r) continue;
-        const uint32_t* o2 = off + (size_t)r2 * (n_dst + 1);
-        uint32_t a = base[r2] + o2[d], b = base[r2] + o2[d + 1];
-        const uint32_t a0 = a;
-        while (a < b) {   // run r2's events of destination d that come before this one
-            const uint32_t m = (a + b) >> 1;
-            const Ev24 y = in[m];
-            if (ev3_less(y.deliver, y.src, y.seq, x.deliver, x.src, x.seq)) a = m + 1; else b = m;
-        }
-        rank += a - a0;
-    }
-    const uint32_t pos = out_off[d] + rank;
-    out_t[pos] = x.deliver;
-    out_s[pos] = x.src;
-    out_q[pos] = x.seq;
-    out_p[pos] = x.pkt;
-}
-
-// merge_runs24 by destination (default): a wave per destination takes the destination's
-// events of every sender run (<= 128: C5 has ~100 per destination), sorts the unique keys
-// (deliver - tmin) << 8 | index with the wave network (wave.h) and stores them in rank order,
-// coalesced -- instead of a thread per event searching every sibling run's segment (a chain of
-// dependent 24-byte loads per run).  A destination with more events, a deliver-time span of
-// 2^24 ns or more, or two equal deliver times (their order needs (src, seq)) is merged by the
-// per-event searches in the same wave.
+// merge_dst24: a wave per destination takes the destination's events of every sender run (<= 128:
+// C5 has ~100 per destination), sorts the unique keys (deliver - tmin) << 8 | index with the wave
+// network (wave.h) and stores them in rank order, coalesced -- a thread per event searching every
+// sibling run's segment (the kernel this one replaced) was a chain of dependent 24-byte loads per
+// run.  A destination with more events, a deliver-time span of 2^24 ns or more, or two equal
+// deliver times (their order needs (src, seq)) is merged by the per-event searches in the same wave.
 __global__ __launch_bounds__(256) void merge_dst24(uint32_t n_runs, uint32_t n_dst, const uint32_t* __restrict__ base,
                                                    const uint32_t* __restrict__ off, const Ev24* __restrict__ in,
                                                    const uint32_t* __restrict__ out_off, uint64_t* __restrict__ out_t,
@@ -2696,7 +1940,7 @@ __global__ __launch_bounds__(256) void merge_dst24(uint32_t n_runs, uint32_t n_d
         }
     }
     if (done) return;
-    // per-event searches (merge_runs24's rank rule) over this destination's events
+    // per-event searches (rank = the events before it in every sibling run) over this destination's events
     for (uint32_t i = lane; i < n; i += 64) {
         uint32_t q0 = 0, at = 0, rank = 0;
         uint32_t acc = 0;   // i's run: the segment counts' running sum
@@ -3007,16 +2251,11 @@ static shd_status relay_round_sharded_x24(shd_ctx* ctx, const shd_batch* b, cons
     SHD_HIP(hipMemcpyAsync(d_base, rbase.data(), (world + 1) * 4, hipMemcpyHostToDevice, s));
     merge_offsets<<<div_up((uint64_t)n_own + 1, 256), 256, 0, s>>>(world, n_own, R.x_roff.as<uint32_t>(),
                                                                   R.m_off.as<uint32_t>());
-    if (n_recv && ctx->knobs.get(K_MERGE_BY_EVENT, 0) != 1)
+    if (n_recv)
         merge_dst24<<<div_up(n_own, 4), 256, 0, s>>>(world, n_own, d_base, R.x_roff.as<uint32_t>(),
                                                      R.x_rrec.as<Ev24>(), R.m_off.as<uint32_t>(),
                                                      R.m_deliver.as<uint64_t>(), R.m_src.as<uint32_t>(),
                                                      R.m_seq.as<uint64_t>(), R.m_pkt.as<uint32_t>());
-    else if (n_recv)
-        merge_runs24<<<div_up(n_recv, 256), 256, 0, s>>>(world, n_own, d_base, R.x_roff.as<uint32_t>(),
-                                                        R.x_rrec.as<Ev24>(), R.m_off.as<uint32_t>(),
-                                                        R.m_deliver.as<uint64_t>(), R.m_src.as<uint32_t>(),
-                                                        R.m_seq.as<uint64_t>(), R.m_pkt.as<uint32_t>());
     SHD_HIP(hipGetLastError());
     SHD_TRY(relay_commit(ctx, &lo));
     SHD_HIP(hipStreamSynchronize(s));   // rbase (host memory) was read by the copy above
@@ -3179,7 +2418,7 @@ static shd_status relay_round_sharded_v7(shd_ctx* ctx, const shd_batch* b, const
                  nullptr, rd->round_end};
         bin_sort_v7<true><<<nb, kB7Threads, 0, s>>>(n_own, nb, nullptr, R.x_rrec.as<uint4>(),
                                                     R.bin_lb.as<unsigned long long>(), R.m_off.as<uint32_t>(), vo,
-                                                    nullptr, ctx->knobs.get(K_B7_STOP, 0), xs);   // (stop: tuning only)
+                                                    nullptr, xs);
     } else {
         xs_fin_empty<<<1, 64, 0, s>>>(xs, R.m_off.as<uint32_t>());
     }
@@ -3190,9 +2429,7 @@ static shd_status relay_round_sharded_v7(shd_ctx* ctx, const shd_batch* b, const
     SHD_TRY(readback_into(ctx, s, R.m_off.as<uint32_t>() + (n_own & ~1u), 16, R.xs_pin.as<unsigned long long>()));
     const uint32_t n_ev = R.xs_pin.as<uint32_t>()[n_own & 1u];
     const shd_status agreed = (shd_status)R.xs_pin.as<uint32_t>()[(n_own & 1u) + 1];
-    // every rank: nothing of the hosts' state is committed (B7_STOP, tuning only: the bin sort
-    // stopped before writing the count and the status)
-    if (agreed != SHD_OK && ctx->knobs.get(K_B7_STOP, 0) == 0) return agreed;
+    if (agreed != SHD_OK) return agreed;   // every rank: nothing of the hosts' state is committed
     R.red_host[0] = hdr(me)[1];
     R.red_host[1] = hdr(me)[2];
     R.red_host[2] = hdr(me)[3];
@@ -3301,14 +2538,9 @@ shd_status shd_relay_setup(shd_ctx* ctx, uint32_t n_hosts, const uint32_t* host_
     if (ctx->comm) SHD_TRY(relay_shard_alloc(ctx));   // shd_relay_round_sharded at any rank count
     {   // v2 needs every path latency < 2^32 ns (max over the table)
         const uint64_t* tl = R.own_table ? R.lat.as<uint64_t>() : ctx->t_lat.as<uint64_t>();
-        SHD_TRY(ctx->g_aux.ensure(8));
-        SHD_HIP(hipMemsetAsync(ctx->g_aux.p, 0, 8, s));
         const uint64_t nn = (uint64_t)n_nodes * n_nodes;
-        max_u64_kernel<<<(uint32_t)std::min<uint64_t>(1024, (nn + 255) / 256), 256, 0, s>>>(
-            tl, nn, reinterpret_cast<unsigned long long*>(ctx->g_aux.p));
         uint64_t mx = 0;
-        SHD_HIP(hipMemcpyAsync(&mx, ctx->g_aux.p, 8, hipMemcpyDeviceToHost, s));
-        SHD_HIP(hipStreamSynchronize(s));
+        SHD_TRY(max_u64_device(ctx, tl, nn, &mx));
         R.table_narrow = (mx >> 32) == 0;
         if (R.table_narrow) {   // packed {lat32, loss} table: one 8-byte gather per packet
             const float* tp = R.own_table ? R.loss.as<float>() : ctx->t_loss.as<float>();

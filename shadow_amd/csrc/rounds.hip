@@ -16,12 +16,65 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "wave.h"
 
 namespace shd {
 
-shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
-
 constexpr uint64_t kEmuMax = ~0ull - 1;   // EmulatedTime::MAX (EMUTIME_MAX = u64::MAX - 1)
+
+// Reductions over a table: the largest path latency (shd_relay_setup: narrow iff it fits 32
+// bits) and the smallest (shd_runahead_setup, shd_routing_min_latency)
+__global__ void max_u64_kernel(const uint64_t* __restrict__ d, uint64_t n,
+                               unsigned long long* __restrict__ out) {
+    uint64_t m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        m = d[i] > m ? d[i] : m;
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(m, o);
+        m = w > m ? w : m;
+    }
+    // one atomic per workgroup: 4 waves per block on one address contend (97 us for 8 MB)
+    __shared__ uint64_t part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) m = part[w] > m ? part[w] : m;
+        atomicMax(out, (unsigned long long)m);
+    }
+}
+
+__global__ void min_u64_kernel(const uint64_t* __restrict__ d, uint64_t n,
+                               unsigned long long* __restrict__ out) {
+    uint64_t m = ~0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
+        m = d[i] < m ? d[i] : m;
+    m = wave_min_u64(m);
+    __shared__ uint64_t part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) m = part[w] < m ? part[w] : m;
+        atomicMin(out, (unsigned long long)m);
+    }
+}
+
+template <bool MAX>
+static shd_status minmax_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out) {
+    SHD_TRY(ctx->g_aux.ensure(8));
+    SHD_HIP(hipMemsetAsync(ctx->g_aux.p, MAX ? 0 : 0xFF, 8, ctx->stream));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
+    (MAX ? max_u64_kernel : min_u64_kernel)<<<grid ? grid : 1, 256, 0, ctx->stream>>>(
+        d, n, reinterpret_cast<unsigned long long*>(ctx->g_aux.p));
+    SHD_HIP(hipMemcpyAsync(out, ctx->g_aux.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SHD_HIP(hipStreamSynchronize(ctx->stream));
+    return SHD_OK;
+}
+shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out) {
+    return minmax_u64_device<false>(ctx, d, n, out);
+}
+shd_status max_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out) {
+    return minmax_u64_device<true>(ctx, d, n, out);
+}
 
 void round_note(shd_ctx* ctx, uint64_t min_deliver, uint64_t min_latency) {
     RoundState& W = ctx->rnd;

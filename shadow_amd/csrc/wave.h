@@ -1,4 +1,4 @@
-// Wave-level exchanges and sorts shared by the relay's destination sorts (relay.hip) and the
+// Wave-level exchanges and sorts shared by the relay's destination sorts (relay_*.hip) and the
 // event queues' per-host merge (equeue.hip): 64-lane gfx950 waves, keys held NPL per lane
 // (element e = lane + 64 c).
 #pragma once
@@ -67,7 +67,13 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v, uint32_t lane) {
     for (uint32_t o = 1; o < 64; o <<= 1) v = max(v, xor_lane(v, o, lane));
     return v;
 }
-
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(v, o);
+        v = w < v ? w : v;
+    }
+    return v;
+}
 
 // Bitonic sort of 64 * NPL keys held NPL per lane (element e = lane + 64 c), ascending.
 template <int NPL>

@@ -364,7 +364,7 @@ def test_device_batch_unaligned_inputs(engine):
 def test_draw_top_bits_at_the_drop_threshold(engine, loss01, above):
     """K0 keeps a draw's top 32 bits only.  The drop test chance >= reliability is
     draw >> 11 >= T = ceil(reliability * 2^53), and for reliability = 1f32 - loss with a loss in
-    [0, 1] T is a multiple of 2^21, so the top bits decide it exactly (relay.hip draw_drops).
+    [0, 1] T is a multiple of 2^21, so the top bits decide it exactly (relay_priv.h draw_drops).
     Host 0's first draw is crafted (Xoshiro256++ output solved for s3) to sit just below or at
     the threshold; the statuses match the oracle's f64 comparison on pipeline 7."""
     from fractions import Fraction
@@ -428,3 +428,45 @@ def test_clamped_deliver_times_tie_everywhere(engine):
     assert np.array_equal(r.status, o["status"]) and np.array_equal(r.ev_off, o["events"]["off"])
     for k in ("deliver", "src", "seq", "pkt"):
         assert np.array_equal(getattr(r, "ev_" + k), o["events"][k]), k
+
+
+RETIRED_KNOBS = ("MERGE_BY_EVENT", "RELAY_K0_INLINE", "B7_STOP")
+KEPT_RELAY_KNOBS = ("RELAY_FORCE_V1", "RELAY_FORCE_V3", "RELAY_NO_LDS_MAP", "RELAY_SHARD_X24",
+                    "RELAY_GROUP_SENDS", "HIST_SCALAR", "RELAY_SCAN2")
+
+
+def test_retired_knobs_are_refused(engine, knob):
+    """The switches that selected a settled loser (the thread-per-event merge, the side-stream
+    K0) or a wrong result (the partial bin sort) are gone: their names are unknown to set_knob and
+    get_knob (SHD_ERR_INVALID), with or without the SHD_ prefix.  Every relay knob that forces a
+    fallback real inputs can also reach is still accepted."""
+    from shadow_amd._native import ShdError
+    for name in RETIRED_KNOBS:
+        for spelled in (name, "SHD_" + name):
+            with pytest.raises(ShdError) as e:
+                engine.set_knob(spelled, 1)
+            assert e.value.code == "INVALID", spelled
+            with pytest.raises(ShdError) as e:
+                engine.get_knob(spelled)
+            assert e.value.code == "INVALID", spelled
+    for name in KEPT_RELAY_KNOBS:
+        knob(name, 1)
+        assert engine.get_knob(name) == 1, name
+
+
+def test_test_fail_is_not_read_from_the_environment():
+    """TEST_FAIL injects failures, so a process environment must not reach it: a fresh engine
+    opened under SHD_TEST_FAIL=1 reads it back unset, while the environment snapshot still works
+    for every other knob (SHD_RELAY_FORCE_V3=1 reads back 1)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("from shadow_amd.routing import Engine\n"
+            "e = Engine(0)\n"
+            "print('knobs', e.get_knob('TEST_FAIL'), e.get_knob('RELAY_FORCE_V3'))\n"
+            "e.close()\n")
+    env = dict(os.environ, SHD_TEST_FAIL="1", SHD_RELAY_FORCE_V3="1")
+    p = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=100)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("knobs ")]
+    assert lines == ["knobs None 1"], p.stdout[-2000:]

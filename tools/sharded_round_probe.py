@@ -7,9 +7,9 @@ all-to-all and its host sync, the 24-byte event packing, the exchange and the pe
 merge of the two senders' runs.  Prints ms per round for both (median of the timed rounds), and
 first the plain device round (shd_relay_round_device) on the same batch, the baseline of the
 sharded entry point's fixed cost (PROBE_RCCL=1: the world-1 leg over RCCL instead of the
-in-process communicator).  Every timed round ends with a device synchronize.  Under
-`rocprofv3 --kernel-trace --memory-copy-trace`, tools/r06_shard_trace.py splits the trace into
-the three legs' rounds and prints one round's phases.
+in-process communicator).  Every timed round ends with a device synchronize, so a
+`rocprofv3 --kernel-trace --memory-copy-trace` of it splits into the three legs' rounds
+(`profiles/r06_sharded_round_trace.txt` is one round's phases from such a trace).
 
     python tools/sharded_round_probe.py [rounds]
 """
