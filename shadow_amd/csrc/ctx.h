@@ -272,6 +272,7 @@ struct PreparedGraph {
     bool dense_rows = false;  // the arc CSR is the complete graph's dense matrix (routing.hip csr_is_dense)
     uint64_t arcs = 0, max_arc_lat = 0, pruned_arcs = 0, tight_arcs = 0;
     uint32_t pruned_pad = 0;   // the pad width of the lists pruned_arcs counted (ArcView::pad)
+    uint32_t pruned_path = 0;  // and the prune kernels that made them (ArcView::path)
     uint32_t mean_arc_lat = 1, min_arc_lat = 1;
     bool reordered = false;   // g_offr / g_usedr / g_arc8r / g_aqr hold the locality order
     bool spread = false;      // g_offs / g_useds / g_arc16s hold the wave-spread order (LDS kernel)
@@ -358,7 +359,7 @@ struct shd_ctx {
     shd::DevBuf d_es, d_ed, d_el, d_ep, d_col;   // direct mode edge arrays
     // routing scratch
     shd::DevBuf g_off, g_dst, g_lat, g_q, g_lat64, g_used, g_diag_lat, g_diag_loss, g_flags,
-        g_dense, g_prune_dst, g_prune_dst2, g_prune_cnt, g_labels, g_aux, g_arc16, g_arc8, g_aq, g_fw, g_glab, g_pred,
+        g_dense, g_prune_dst, g_prune_dst2, g_prune_cnt, g_prune_nn, g_labels, g_aux, g_arc16, g_arc8, g_aq, g_fw, g_glab, g_pred,
         g_offr, g_usedr, g_arc8r, g_aqr,   // locality-ordered copies (global-label kernel)
         g_offs, g_useds, g_arc16s;         // wave-spread copies (1024-thread LDS kernel)
     uint32_t* nh_out = nullptr;   // next-hop rows of the running build (shd_routing_run_next_hops)

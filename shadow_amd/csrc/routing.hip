@@ -1335,51 +1335,26 @@ __device__ __forceinline__ uint32_t dense_lat(const uint32_t* __restrict__ Wl, u
     else return Wl[(size_t)x * V + v];
 }
 
-constexpr uint32_t kPad1 = 64, kPad2 = 32;   // list padding in slots: prune_rows, prune_rows2
-template <int BLOCK, int K, bool DCSR = false, int VB = 4, int KB = 8, bool CMP = false, int PB = 8>
-__global__ __launch_bounds__(BLOCK) void prune_rows(
-    const uint32_t* __restrict__ Wl, const float* __restrict__ Wp, uint32_t V,
-    uint32_t* __restrict__ pbeg, uint32_t* __restrict__ pend, uint4* __restrict__ parcs,
-    uint32_t* __restrict__ cursor, uint32_t* __restrict__ flags, uint32_t shg = 0xFFFFFFFFu) {
-    // Detour nodes x: ~K of u's lowest-latency neighbours, chosen by a 256-bin latency histogram
-    // (every node in the bins below the K-th smallest latency's bin, then nodes of that bin in
-    // index order up to K).  Any set of detour nodes is sound -- it only decides how many arcs
-    // are dropped -- so this replaces a full bitonic sort of the row (55 barrier stages) by
-    // three passes over it.
-    // CMP (round 5, the K = 32 default; C2 prune 24.4 -> 15.6 us): the detours are the K
-    // smallest (latency, index) pairs in ascending order, ranked in LDS by all waves; the first
-    // batch tests every arc against the KB nearest, skipping detours no shorter than the arc; its
-    // survivors (~11 % of a C2 row) are packed and tested one lane each against the rest, PB at a
-    // time, stopping at the first detour no shorter than the arc -- instead of every wave
-    // carrying a few live lanes through every batch.  The row's losses come in with its
-    // latencies, so the kept arcs read them from LDS.
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint4* kept = reinterpret_cast<uint4*>(smem);      // V staged arcs
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(kept + V);   // [0] kept [1] base [2] max [3] below-bin
-    uint32_t* hist = cnt + 8;                          // 256 bins
-    uint32_t* selx = hist + 256;                       // K detour nodes
-    uint32_t* sela = selx + K;                         // their latencies
-    uint32_t* row = sela + K;                          // u's exact arc latencies
-    uint16_t* binv = reinterpret_cast<uint16_t*>(row + V);   // bin per node (0xFFFF: no arc)
-    uint2* live2 = reinterpret_cast<uint2*>((reinterpret_cast<uintptr_t>(binv + V) + 7) & ~(uintptr_t)7);   // CMP: first-batch survivors
-    uint64_t* cand = reinterpret_cast<uint64_t*>(live2 + V);   // CMP: <= 64 detour candidates
-    uint32_t* rk = reinterpret_cast<uint32_t*>(cand + 64);        // and their ranks
-    float* prow = reinterpret_cast<float*>(rk + 64);              // CMP: u's arc losses
-    const uint32_t u = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-#ifdef SHD_SSSP_PROF
-    uint64_t pr_acc[6] = {0, 0, 0, 0, 0, 0}, pr_t = __builtin_amdgcn_s_memtime();
-    const uint64_t pr_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (DCSR && u == 0 && tid < 16) flags[tid] = (tid == 4 || tid == 5) ? 0xFFFFFFFFu : 0u;   // as flags_init
-    uint32_t mx = 0;
-    for (uint32_t v = tid; v < V; v += BLOCK) {
-        const uint32_t w = dense_lat<DCSR>(Wl, V, u, v);
-        row[v] = w;
-        if (w != kLat32Inf) mx = max(mx, w);
-        if constexpr (CMP) {   // the row's losses ride the same memory trip (kept arcs read them)
-            if (w != kLat32Inf) prow[v] = Wp[DCSR ? (size_t)u * (V - 1) + v - (v > u ? 1u : 0u) : (size_t)u * V + v];
-        }
-    }
+// The detour selection shared by prune_rows and nearest_rows: the K nearest out-arcs of the row
+// held in LDS (row[v]: latency or +inf; mx: this thread's largest finite one), left in
+// selx / sela (unused slots: node 0, latency +inf).  Detour nodes x: ~K of u's lowest-latency
+// neighbours, chosen by a 256-bin latency histogram (every node in the bins below the K-th
+// smallest latency's bin, then nodes of that bin in index order up to K).  CMP: exactly the K
+// smallest (latency, index) pairs in ascending order, ranked in LDS by all waves.  Ends with a
+// barrier; cnt[0] (kept arcs) and cnt[7] (first-batch survivors) are reset for the caller.
+struct SelectLds {
+    uint32_t *cnt, *hist, *selx, *sela, *row;   // [8], [256], [K], [K], [V]
+    uint16_t* binv;                             // [V] bin per node (0xFFFF: no arc)
+    uint64_t* cand;                             // CMP: [64] detour candidates
+    uint32_t* rk;                               // CMP: [64] their ranks
+};
+template <int BLOCK, int K, bool CMP, class Mark>
+__device__ __forceinline__ void select_nearest(const SelectLds& L, uint32_t V, uint32_t mx, uint32_t shg, Mark&& mark) {
+    uint32_t *const cnt = L.cnt, *const hist = L.hist, *const selx = L.selx, *const sela = L.sela, *const row = L.row;
+    uint16_t* const binv = L.binv;
+    uint64_t* const cand = L.cand;
+    uint32_t* const rk = L.rk;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
     for (uint32_t i = tid; i < 256; i += BLOCK) hist[i] = 0;
     if (tid < 8) cnt[tid] = 0;
     if (CMP && tid < 64) rk[tid] = 0;
@@ -1395,14 +1370,14 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
         const uint32_t bits = 32u - (uint32_t)__clz((int)max(cnt[2], 1u));
         sh = bits > 8 ? bits - 8 : 0;
     }
-    PR_MARK(0);
+    mark(0);
     for (uint32_t v = tid; v < V; v += BLOCK) {
         const uint32_t w = row[v];
         binv[v] = w != kLat32Inf ? (uint16_t)(w >> sh) : (uint16_t)0xFFFF;
         if (w != kLat32Inf) atomicAdd(&hist[w >> sh], 1u);
     }
     __syncthreads();
-    PR_MARK(1);
+    mark(1);
     if (tid < 64) {   // wave 0: the bin holding the K-th smallest latency
         uint32_t c[4], sum = 0;
 #pragma unroll
@@ -1442,7 +1417,7 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
         }
     }
     __syncthreads();
-    PR_MARK(2);
+    mark(2);
     // CMP: the detours are the K smallest (latency, index) pairs in ascending order.  Fast path:
     // the bins below and the boundary bin hold at most 64 candidates -- collect them, and wave 0
     // sorts them in registers; otherwise the index-order boundary scan below, then a rank sort.
@@ -1531,6 +1506,7 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
                 for (uint32_t i = lane; i < (uint32_t)K; i += 64) {
                     const uint32_t ai = sela[i], xi = selx[i];
                     uint32_t r = 0;
+#pragma unroll 4   // (unrolled whole, the K flags are summed at the end: > 64 VGPRs)
                     for (uint32_t j = 0; j < (uint32_t)K; ++j) {
                         const uint32_t aj = sela[j], xj = selx[j];
                         r += aj < ai || (aj == ai && (xj < xi || (xj == xi && j < i))) ? 1u : 0u;
@@ -1548,6 +1524,53 @@ __global__ __launch_bounds__(BLOCK) void prune_rows(
         }
     }
     __syncthreads();
+}
+
+constexpr uint32_t kPad1 = 64, kPad2 = 32;   // list padding in slots: prune_rows, prune_rows2
+template <int BLOCK, int K, bool DCSR = false, int VB = 4, int KB = 8, bool CMP = false, int PB = 8>
+__global__ __launch_bounds__(BLOCK) void prune_rows(
+    const uint32_t* __restrict__ Wl, const float* __restrict__ Wp, uint32_t V,
+    uint32_t* __restrict__ pbeg, uint32_t* __restrict__ pend, uint4* __restrict__ parcs,
+    uint32_t* __restrict__ cursor, uint32_t* __restrict__ flags, uint32_t shg = 0xFFFFFFFFu) {
+    // Detour nodes x: ~K of u's lowest-latency neighbours (select_nearest).  Any set of detour
+    // nodes is sound -- it only decides how many arcs are dropped -- so this replaces a full
+    // bitonic sort of the row (55 barrier stages) by three passes over it.
+    // CMP (round 5, the K = 32 default; C2 prune 24.4 -> 15.6 us): the detours are the K
+    // smallest (latency, index) pairs in ascending order, ranked in LDS by all waves; the first
+    // batch tests every arc against the KB nearest, skipping detours no shorter than the arc; its
+    // survivors (~11 % of a C2 row) are packed and tested one lane each against the rest, PB at a
+    // time, stopping at the first detour no shorter than the arc -- instead of every wave
+    // carrying a few live lanes through every batch.  The row's losses come in with its
+    // latencies, so the kept arcs read them from LDS.
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint4* kept = reinterpret_cast<uint4*>(smem);      // V staged arcs
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(kept + V);   // [0] kept [1] base [2] max [3] below-bin
+    uint32_t* hist = cnt + 8;                          // 256 bins
+    uint32_t* selx = hist + 256;                       // K detour nodes
+    uint32_t* sela = selx + K;                         // their latencies
+    uint32_t* row = sela + K;                          // u's exact arc latencies
+    uint16_t* binv = reinterpret_cast<uint16_t*>(row + V);   // bin per node (0xFFFF: no arc)
+    uint2* live2 = reinterpret_cast<uint2*>((reinterpret_cast<uintptr_t>(binv + V) + 7) & ~(uintptr_t)7);   // CMP: first-batch survivors
+    uint64_t* cand = reinterpret_cast<uint64_t*>(live2 + V);   // CMP: <= 64 detour candidates
+    uint32_t* rk = reinterpret_cast<uint32_t*>(cand + 64);        // and their ranks
+    float* prow = reinterpret_cast<float*>(rk + 64);              // CMP: u's arc losses
+    const uint32_t u = blockIdx.x, tid = threadIdx.x;
+#ifdef SHD_SSSP_PROF
+    uint64_t pr_acc[6] = {0, 0, 0, 0, 0, 0}, pr_t = __builtin_amdgcn_s_memtime();
+    const uint64_t pr_t0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    if (DCSR && u == 0 && tid < 16) flags[tid] = (tid == 4 || tid == 5) ? 0xFFFFFFFFu : 0u;   // as flags_init
+    uint32_t mx = 0;
+    for (uint32_t v = tid; v < V; v += BLOCK) {
+        const uint32_t w = dense_lat<DCSR>(Wl, V, u, v);
+        row[v] = w;
+        if (w != kLat32Inf) mx = max(mx, w);
+        if constexpr (CMP) {   // the row's losses ride the same memory trip (kept arcs read them)
+            if (w != kLat32Inf) prow[v] = Wp[DCSR ? (size_t)u * (V - 1) + v - (v > u ? 1u : 0u) : (size_t)u * V + v];
+        }
+    }
+    select_nearest<BLOCK, K, CMP>(SelectLds{cnt, hist, selx, sela, row, binv, cand, rk}, V, mx, shg,
+                                  [&](int slot) { (void)slot; PR_MARK(slot); });
     PR_MARK(3);
     // 2-hop test of every arc of u: each thread tests VB arcs at once against batches of KB
     // detours (VB x KB loads in flight), and a lane stops loading for an arc as soon as a
@@ -1810,6 +1833,201 @@ __global__ __launch_bounds__(kP2Block) void prune_rows2(
             pbeg[u] = at;
             pend[u] = at + n2;
         }
+    }
+}
+
+// The fused prune (the K = 32 default; SHD_PRUNE_FUSED=0: prune_rows + prune_rows2 above): two
+// launches whose rows each make three to four dependent memory trips, instead of two whose rows
+// make nine.  prune_rows' survivor pass over detours 8..31 and the hand-over of its lists to
+// prune_rows2 fall away: the 3-hop test is the stronger one and runs on the first batch's
+// survivors directly, its candidates coming from a per-node nearest-neighbour table instead of
+// other rows' stage-1 lists.
+//
+// nearest_rows: NN[x][0..kNear) = {node, latency} of x's kNear smallest (latency, index)
+// out-arcs in ascending order (select_nearest, CMP: the detours prune_rows picks), unused
+// entries {0xFFFFFFFF, +inf}; 256 B per node.
+constexpr uint32_t kNear = 32;
+static size_t nearest_lds_bytes(uint32_t V) { return 64 * 12 + (8 + 256 + 2 * kNear + (size_t)V) * 4 + (size_t)V * 2; }
+template <int BLOCK, bool DCSR>
+__global__ __launch_bounds__(BLOCK, BLOCK / 64) void nearest_rows(   // 8 waves per SIMD at BLOCK = 512
+    const uint32_t* __restrict__ Wl, uint32_t V, uint2* __restrict__ NN, uint32_t* __restrict__ flags, uint32_t shg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* cand = reinterpret_cast<uint64_t*>(smem);
+    uint32_t* rk = reinterpret_cast<uint32_t*>(cand + 64);
+    uint32_t* cnt = rk + 64;
+    uint32_t* hist = cnt + 8;
+    uint32_t* selx = hist + 256;
+    uint32_t* sela = selx + kNear;
+    uint32_t* row = sela + kNear;
+    uint16_t* binv = reinterpret_cast<uint16_t*>(row + V);
+    const uint32_t x = blockIdx.x, tid = threadIdx.x;
+    if (DCSR && x == 0 && tid < 16) flags[tid] = (tid == 4 || tid == 5) ? 0xFFFFFFFFu : 0u;   // as flags_init
+    uint32_t mx = 0;
+    for (uint32_t v = tid; v < V; v += BLOCK) {
+        const uint32_t w = v == x ? kLat32Inf : dense_lat<DCSR>(Wl, V, x, v);
+        row[v] = w;
+        if (w != kLat32Inf) mx = max(mx, w);
+    }
+    select_nearest<BLOCK, (int)kNear, true>(SelectLds{cnt, hist, selx, sela, row, binv, cand, rk}, V, mx, shg, [](int) {});
+    if (tid < kNear) {
+        const uint32_t a = sela[tid];
+        NN[(size_t)x * kNear + tid] = make_uint2(a != kLat32Inf ? selx[tid] : 0xFFFFFFFFu, a);
+    }
+}
+
+// prune_fused, one workgroup per row u:
+//   S1(u)  the arcs (u, v) that survive prune_rows' first batch: no detour u -> x -> v over the
+//          kPfFirst nearest x = NN[u][0..kPfFirst) is strictly shorter (a detour node no nearer
+//          than the arc is skipped); ~119 arcs of a C2 row, every arc of a constant-latency one.
+//   d2[y]  min(lat(u, y), min over x in S1(u) and (y, l) in NN[x], y != u, of lat(u, x) + l)
+//          -- a walk u (-> x) -> y.
+//   (u, v), v in S1(u), is dropped iff some y in NN[v], y != u, y != v, has
+//          d2[y] + lat(y, v) < lat(u, v), lat(y, v) the arc y -> v of the dense matrix (NN[v] only
+//          names the candidates: on a directed graph lat(v, y) is another number).  SYM, an
+//          undirected graph: the matrix is symmetric, so lat(y, v) is the latency NN[v] holds
+//          beside y and the gather falls away (C2: 20.8 -> 14.7 us).
+// Soundness is prune_rows2's: every compared detour is a walk of real arcs with their own
+// latencies, so a tight arc is never dropped whatever the candidate sets are, and ties keep the
+// arc.  The sums are guarded as there (a two-term sum that wraps or reaches +inf is no walk; the
+// three-term sum is formed in 64 bits).
+// Memory trips: the row (latencies, losses) and NN[u]; the first batch's gathers; NN[x] of the
+// S1 nodes, a half-wave per 256-B list; the lat(y, v) gathers of the pairs with d2[y] below
+// lat(u, v) (not SYM); the list write.  The lists are taken kPfRound = 16 kPfLists at a time,
+// kPfLists per half-wave (SYM 12: one round covers C2's longest S1, 151; 8 with the gather's
+// registers), so registers stay bounded for any |S1|: every round lowers d2 first (last round
+// first, so round 0's lists are still in registers), then after one barrier every round is
+// tested, rounds past the first reading their lists again (L2 hits).  d2 is complete before the
+// first test, d2 is a minimum and a drop flag is only ever set, so the kept set is a function of
+// the graph alone, whatever order the first batch's atomics filled S1 in; only the order of a
+// final list follows it.  No list is cut off or copied through.
+// The final list goes to row u's fixed offset, padded to kPad2 slots with prune_rows2's no-op arcs.
+constexpr int kPfBlock = 512, kPfFirst = 8;
+static size_t fused_lds_bytes(uint32_t V) { return (size_t)V * 20 + (2 * kNear + 8) * 4; }
+template <bool DCSR, bool SYM>
+__global__ __launch_bounds__(kPfBlock, 8) void prune_fused(   // 8 waves per SIMD: four workgroups per CU
+    const uint32_t* __restrict__ Wl, const float* __restrict__ Wp, uint32_t V, const uint2* __restrict__ NN,
+    uint32_t* __restrict__ pbeg, uint32_t* __restrict__ pend, uint4* __restrict__ parcs) {
+    static_assert(kNear == 32 && (kPfFirst == 8 || kPfFirst == 16), "a half-wave per list");
+    constexpr int kPfLists = SYM ? 12 : 8;   // lists per half-wave and round (the gather form holds dy / lyv too)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint2* s1 = reinterpret_cast<uint2*>(smem);         // [V] S1(u): {v, lat(u, v)}, in arrival order
+    uint32_t* d2 = reinterpret_cast<uint32_t*>(s1 + V); // [V] u's latency row, then the 2-hop row
+    float* prow = reinterpret_cast<float*>(d2 + V);     // [V] u's arc losses
+    uint32_t* drop = reinterpret_cast<uint32_t*>(prow + V);   // [V] S1 arc j falls
+    uint32_t* nnx = drop + V;                           // NN[u]: nodes
+    uint32_t* nna = nnx + kNear;                        //        latencies
+    uint32_t* cnt = nna + kNear;                        // [0] |S1| [1] kept
+    const uint32_t u = blockIdx.x, tid = threadIdx.x;
+    const uint32_t rs = DCSR ? V - 1 : V;               // row stride of the matrix (V <= 4096: indices fit u32)
+    for (uint32_t v = tid; v < V; v += kPfBlock) {
+        const uint32_t w = v == u ? kLat32Inf : dense_lat<DCSR>(Wl, V, u, v);
+        d2[v] = w;
+        drop[v] = 0u;
+        if (w != kLat32Inf) prow[v] = Wp[(size_t)u * rs + v - (DCSR && v > u ? 1u : 0u)];
+    }
+    if (tid < kNear) {
+        const uint2 e = NN[(size_t)u * kNear + tid];
+        nnx[tid] = e.x;
+        nna[tid] = e.y;
+    }
+    if (tid < 8) cnt[tid] = 0u;
+    __syncthreads();
+    // the first batch: VB arcs per thread against the kPfFirst nearest detours, 16 loads in flight
+    constexpr int VB = 16 / kPfFirst;
+    for (uint32_t v0 = tid; v0 < V; v0 += kPfBlock * VB) {
+        uint32_t w[VB], z[VB], bv[VB][kPfFirst], as[kPfFirst];
+#pragma unroll
+        for (int i = 0; i < VB; ++i) {
+            const uint32_t v = v0 + i * kPfBlock;
+            w[i] = v < V ? d2[v] : kLat32Inf;
+            z[i] = kLat32Inf;
+        }
+#pragma unroll
+        for (int j = 0; j < kPfFirst; ++j) {
+            as[j] = nna[j];
+            const uint32_t x = nnx[j];
+#pragma unroll
+            for (int i = 0; i < VB; ++i) {
+                const uint32_t v = v0 + i * kPfBlock;
+                // (an unused entry has latency +inf, a missing arc w = +inf: neither loads)
+                bv[i][j] = w[i] != kLat32Inf && as[j] < w[i] && v != x ? Wl[x * rs + v - (DCSR && v > x ? 1u : 0u)]
+                                                                       : kLat32Inf;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < VB; ++i) {
+#pragma unroll
+            for (int j = 0; j < kPfFirst; ++j) {
+                const uint32_t t = as[j] + bv[i][j];
+                if (bv[i][j] != kLat32Inf && t >= as[j]) z[i] = min(z[i], t);
+            }
+            if (w[i] != kLat32Inf && w[i] <= z[i]) s1[atomicAdd(&cnt[0], 1u)] = make_uint2(v0 + i * kPfBlock, w[i]);
+        }
+    }
+    __syncthreads();
+    constexpr uint32_t kPfRound = (kPfBlock / 32) * kPfLists;
+    const uint32_t n1 = cnt[0], rounds = (n1 + kPfRound - 1) / kPfRound;
+    const uint32_t hw = tid >> 5, sl = tid & 31;
+    uint2 pr[kPfLists];   // entry sl of this half-wave's lists: {y, lat(x, y)}
+    auto load_round = [&](uint32_t r) {
+#pragma unroll
+        for (int k = 0; k < kPfLists; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
+            pr[k] = make_uint2(0xFFFFFFFFu, kLat32Inf);
+            if (j < n1) pr[k] = NN[(size_t)s1[j].x * kNear + sl];
+        }
+    };
+    for (uint32_t r = rounds; r-- > 0;) {   // d2 over the walks u -> x -> y
+        load_round(r);
+#pragma unroll
+        for (int k = 0; k < kPfLists; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
+            if (j >= n1) continue;
+            const uint32_t y = pr[k].x, l1 = s1[j].y, t = l1 + pr[k].y;
+            if (y < V && y != u && pr[k].y != kLat32Inf && t >= l1 && t != kLat32Inf) atomicMin(&d2[y], t);
+        }
+    }
+    __syncthreads();
+    for (uint32_t r = 0; r < rounds; ++r) {   // (u, v = list j's node) against u ~> y -> v
+        if (r) load_round(r);
+        uint32_t dy[kPfLists], lyv[kPfLists];
+#pragma unroll
+        for (int k = 0; k < kPfLists; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
+            dy[k] = kLat32Inf;
+            lyv[k] = kLat32Inf;
+            if (j >= n1) continue;
+            const uint2 e = s1[j];
+            const uint32_t y = pr[k].x;
+            if (y >= V || y == u || y == e.x) continue;
+            const uint32_t d = d2[y];
+            // (a walk no shorter than the arc before its last step cannot beat it: no load)
+            if (d < e.y) {
+                dy[k] = d;
+                // SYM (undirected graphs): lat(y, v) = lat(v, y), which NN[v] holds -- no gather
+                lyv[k] = SYM ? pr[k].y : Wl[y * rs + e.x - (DCSR && e.x > y ? 1u : 0u)];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPfLists; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
+            if (j < n1 && lyv[k] != kLat32Inf && dy[k] != kLat32Inf && (uint64_t)dy[k] + lyv[k] < (uint64_t)s1[j].y)
+                drop[j] = 1u;
+        }
+    }
+    __syncthreads();
+    const uint32_t at = u * ((V + kPad1 - 1) / kPad1 * kPad1);   // the row's fixed offset (prune_rows2's)
+    for (uint32_t j = tid; j < n1; j += kPfBlock) {
+        if (drop[j]) continue;
+        const uint2 e = s1[j];
+        parcs[at + atomicAdd(&cnt[1], 1u)] = make_uint4(e.x, e.y, __float_as_uint(one_minus(prow[e.x])), 0u);
+    }
+    __syncthreads();
+    const uint32_t n2 = cnt[1], np = (n2 + kPad2 - 1) / kPad2 * kPad2;
+    for (uint32_t i = n2 + tid; i < np; i += kPfBlock) parcs[at + i] = make_uint4(V + (i & 63u), 0u, 0u, 0u);
+    if (tid == 0) {
+        pbeg[u] = at;
+        pend[u] = at + n2;
     }
 }
 
@@ -2344,6 +2562,7 @@ struct ArcView {
     uint64_t n_arcs;
     uint32_t pad = 0;      // lists padded to this many slots with no-op arcs (prune_rows 64, prune_rows2 32; 0: not)
     const uint32_t* used = nullptr;   // a relabelled copy (prepare_spread): the used nodes' new ids
+    uint32_t path = 0;     // run_prune: which prune kernels made the lists (count_kept recounts when it changes)
 };
 
 template <int BLOCK, int G, bool CACHE>
@@ -2624,7 +2843,8 @@ constexpr uint32_t kPruneMaxV = 4096;
 constexpr uint32_t kBlockedMaxV = 16384;   // closure matrix <= 1 GiB
 
 // Dense arc matrix + k-nearest 2-hop prune over all V rows -> pruned arc lists (row stride V),
-// then the 3-hop stage over those lists (prune_rows2; SHD_PRUNE_STAGE2=0: stage 1 alone, 64-slot lists).
+// then the 3-hop stage over those lists (prune_rows2; SHD_PRUNE_STAGE2=0: stage 1 alone, 64-slot lists);
+// by default both in one pass over the first batch's survivors (nearest_rows + prune_fused).
 static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
     PreparedGraph& P = ctx->prep;
     hipStream_t s = ctx->stream;
@@ -2635,14 +2855,12 @@ static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
 #else
     const bool stage2 = ctx->knobs.get(K_PRUNE_STAGE2, 1) != 0;
 #endif
-    SHD_TRY(ctx->g_prune_dst.ensure((nn + (uint64_t)V * kPad1) * 16));   // + list padding
     SHD_TRY(ctx->g_prune_cnt.ensure((size_t)V * 16 + 16));
     uint32_t* pbeg = ctx->g_prune_cnt.as<uint32_t>();
     uint32_t* pend = pbeg + V;
     uint32_t* cursor = pend + V;
     uint32_t* pbeg2 = cursor + 4;   // the final lists' ranges (stage 2)
     uint32_t* pend2 = pbeg2 + V;
-    uint4* pa = ctx->g_prune_dst.as<uint4>();
     uint32_t* flags = ctx->g_flags.as<uint32_t>();
     const uint32_t Kr = ctx->knobs.get(K_PRUNE_K, kPruneK);   // tuning: detour nodes per row (same output tables)
     const uint32_t K = Kr >= 128 ? 128u : Kr >= 64 ? 64u : 32u;
@@ -2655,6 +2873,43 @@ static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
     const uint32_t gbits = 64u - (uint32_t)__builtin_clzll(std::max<uint64_t>(std::min<uint64_t>(P.max_arc_lat, kLat32Inf - 1), 1));
     const uint32_t shg = ctx->knobs.get(K_PRUNE_SHAPE_SH, 1) ? (gbits > 8 ? gbits - 8 : 0) : 0xFFFFFFFFu;
     const bool dcsr = P.dense_rows && !ctx->knobs.on(K_PRUNE_DENSE_BUILD);
+    // K = 32, the default shape and stage 2 on: nearest_rows + prune_fused (SHD_PRUNE_FUSED=0: the
+    // two kernels below).  The path id tells count_kept which kernels made the lists it counted.
+    const bool fused = K == 32 && !legacy && stage2 && ctx->knobs.get(K_PRUNE_FUSED, 1) != 0;
+    const uint32_t path = K | (legacy ? 1u << 8 : 0u) | (stage2 ? 1u << 9 : 0u) | (fused ? 1u << 10 : 0u);
+    const uint64_t stride = ((uint64_t)V + kPad1 - 1) / kPad1 * kPad1;   // a row's fixed offset: u * stride
+    if (fused) {
+        SHD_TRY(ctx->g_prune_nn.ensure(std::max<uint64_t>(V, 1) * kNear * 8));
+        SHD_TRY(ctx->g_prune_dst2.ensure(std::max<uint64_t>(V * stride, 1) * 16));
+        uint2* nnb = ctx->g_prune_nn.as<uint2>();
+        uint4* pa2 = ctx->g_prune_dst2.as<uint4>();
+        const size_t ldn = nearest_lds_bytes(V), ldf = fused_lds_bytes(V);
+        // an undirected graph's matrix is symmetric: lat(y, v) comes with NN[v], no gather (SYM)
+        const bool sym = !P.directed;
+        if (dcsr) {
+            const uint32_t* Wl = ctx->g_lat.as<uint32_t>();
+            nearest_rows<512, true><<<V, 512, ldn, s>>>(Wl, V, nnb, flags, shg);
+            const float* Wp = ctx->g_aux.as<float>();
+            if (sym) prune_fused<true, true><<<V, kPfBlock, ldf, s>>>(Wl, Wp, V, nnb, pbeg2, pend2, pa2);
+            else prune_fused<true, false><<<V, kPfBlock, ldf, s>>>(Wl, Wp, V, nnb, pbeg2, pend2, pa2);
+        } else {
+            SHD_TRY(ctx->g_dense.ensure(nn * 8));
+            SHD_TRY(ctx->g_labels.ensure(nn * 4));
+            float* Wp = ctx->g_dense.as<float>();
+            uint32_t* Wl = ctx->g_labels.as<uint32_t>();
+            dense_build<<<V, 256, (size_t)V * 8, s>>>(ctx->g_off.as<uint32_t>(), ctx->g_dst.as<uint32_t>(),
+                                                      ctx->g_lat.as<uint32_t>(), ctx->g_aux.as<float>(), V, Wp, Wl, cursor,
+                                                      flags);
+            nearest_rows<512, false><<<V, 512, ldn, s>>>(Wl, V, nnb, flags, shg);
+            if (sym) prune_fused<false, true><<<V, kPfBlock, ldf, s>>>(Wl, Wp, V, nnb, pbeg2, pend2, pa2);
+            else prune_fused<false, false><<<V, kPfBlock, ldf, s>>>(Wl, Wp, V, nnb, pbeg2, pend2, pa2);
+        }
+        SHD_HIP(hipGetLastError());
+        *out = ArcView{pbeg2, pend2, pa2, 0, kPad2, nullptr, path};
+        return SHD_OK;
+    }
+    SHD_TRY(ctx->g_prune_dst.ensure((nn + (uint64_t)V * kPad1) * 16));   // + list padding
+    uint4* pa = ctx->g_prune_dst.as<uint4>();
     if (dcsr) {
         // the CSR is the dense matrix (complete graph, arcs in index order): prune straight from it
         const uint32_t* Wl = ctx->g_lat.as<uint32_t>();
@@ -2677,18 +2932,17 @@ static shd_status run_prune(shd_ctx* ctx, ArcView* out) {
         else prune_rows<512, 32, false, 2, 8, true, 12><<<V, 512, plds_c, s>>>(Wl, Wp, V, pbeg, pend, pa, cursor, flags, shg);
     }
     SHD_HIP(hipGetLastError());
-    *out = ArcView{pbeg, pend, ctx->g_prune_dst.as<uint4>(), 0, kPad1};
+    *out = ArcView{pbeg, pend, ctx->g_prune_dst.as<uint4>(), 0, kPad1, nullptr, path};
     if (!stage2) return SHD_OK;
     // stage 2 reads other rows' stage-1 lists while it runs: its lists go to a second buffer, each
     // at its row's stage-1 offset (a final list is no longer than the stage-1 one)
-    const uint64_t stride = ((uint64_t)V + kPad1 - 1) / kPad1 * kPad1;
     SHD_TRY(ctx->g_prune_dst2.ensure(std::max<uint64_t>(V * stride, 1) * 16));
     uint4* pa2 = ctx->g_prune_dst2.as<uint4>();
     const size_t lds2 = prune2_lds_bytes(V);
     if (dcsr) prune_rows2<true><<<V, kP2Block, lds2, s>>>(ctx->g_lat.as<uint32_t>(), V, pbeg, pend, pa, pbeg2, pend2, pa2);
     else prune_rows2<false><<<V, kP2Block, lds2, s>>>(ctx->g_labels.as<uint32_t>(), V, pbeg, pend, pa, pbeg2, pend2, pa2);
     SHD_HIP(hipGetLastError());
-    *out = ArcView{pbeg2, pend2, pa2, 0, kPad2};
+    *out = ArcView{pbeg2, pend2, pa2, 0, kPad2, nullptr, path};
     return SHD_OK;
 }
 
@@ -2702,6 +2956,7 @@ static shd_status count_kept(shd_ctx* ctx, const ArcView& A) {
     ctx->info.arcs_kept = k;
     ctx->prep.pruned_arcs = k;
     ctx->prep.pruned_pad = A.pad;
+    ctx->prep.pruned_path = A.path;
     return SHD_OK;
 }
 
@@ -2945,8 +3200,8 @@ shd_status routing_run_impl(shd_ctx* ctx, uint32_t algo, uint32_t rb, uint32_t r
             SHD_TRY(run_prune(ctx, &A));
             // the kept-arc count steers the lane-group width: counted once per prepared graph,
             // before its first SSSP launch, so every build (the first too) runs the same kernel
-            // (again if SHD_PRUNE_STAGE2 changed between two builds of one prepared graph)
-            if (P.pruned_arcs == 0 || P.pruned_pad != A.pad) SHD_TRY(count_kept(ctx, A));
+            // (again if a knob changed the prune path between two builds of one prepared graph)
+            if (P.pruned_arcs == 0 || P.pruned_pad != A.pad || P.pruned_path != A.path) SHD_TRY(count_kept(ctx, A));
             A.n_arcs = P.pruned_arcs;
         }
         bool ovf = false;
