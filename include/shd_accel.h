@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 8
+#define SHD_ABI_VERSION 9
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -695,7 +695,10 @@ shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_tim
  * overtaken, not by a local packet and not by a lower priority (head-of-line blocking).
  * Exactness (FIFO): the merge is exact whenever a host's offers at one instant arrive in
  * increasing priority -- everything but a same-instant retransmission -- and also when the bucket
- * does not block at that instant.
+ * does not block at that instant.  Under SHD_QDISC_FIFO_SOCKETS (below) a same-instant
+ * retransmission is exact as well: the order within a socket is the offer order, whatever the
+ * priorities.  What stays inexact there is two events of one host at the same nanosecond, as
+ * under round-robin.
  *
  * The queuing discipline is interface_qdisc (configuration.rs:396-397, :930-933), chosen at the
  * setup.  Under SHD_QDISC_ROUND_ROBIN (network_interface.c:235-273, :366-392;
@@ -712,8 +715,28 @@ shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_tim
  * one event (one accumulation under relay/mod.rs:124-126) or to one socket.  Two events on one
  * host at the same nanosecond that offer on different sockets are rotated together here; in the
  * reference the first event's task may already have drained its packets.  Within a socket packets
- * leave in offer order: the socket's separate control buffer (socket.c:467, control packets
- * first) is not modelled.
+ * leave in offer order: SHD_QDISC_FIFO and SHD_QDISC_ROUND_ROBIN see a socket as one list.
+ *
+ * The reference's sockets have two: a packet of priority 0 goes to the socket's control buffer,
+ * every other one to its data buffer (socket.c:432-437), and peek and pull take the control buffer
+ * first (socket.c:182-189, :466-467).  Every TCP control packet -- a pure ACK, SYN, FIN -- has
+ * priority 0 (tcp.c:947-963; the host's counter starts at 1, host.rs:248), so a TCP host soon has
+ * two packets of priority 0 queued, which SHD_QDISC_FIFO refuses.  SHD_QDISC_FIFO_SOCKETS and
+ * SHD_QDISC_ROUND_ROBIN_SOCKETS model both buffers; an offer then carries the packet's priority
+ * (0: control) and the offering socket's canonical handle (shd_outbound_advance_sockets).  Per
+ * host: a set of sockets keyed by handle, each with a control list and a data list in offer order;
+ * the socket's head is its first control packet if it has one, else its first data packet; a
+ * socket is queued exactly while it has a packet.
+ *   SHD_QDISC_FIFO_SOCKETS   the queue is the array heap of priority_queue.c:87-140, :189-208
+ *       under network_queuing_disciplines.c:90-102: smaller(i, j) = !(key(i) > key(j)), key = the
+ *       socket's head priority now, a tie "smaller" both ways.  Push appends and sifts up; pop
+ *       swaps the root with the last entry, shrinks and sifts down (the right child when
+ *       smaller(right, left)).  The discipline (network_interface.c:276-316) pops the root socket,
+ *       pulls its head packet and pushes the socket again if it still has data, before the relay
+ *       knows whether the bucket blocks.  A control packet offered to a socket that is in the heap
+ *       changes its key where it stands, nothing is re-heapified: the send order is a function of
+ *       the heap array, not "lowest priority first", and the device keeps that array.
+ *   SHD_QDISC_ROUND_ROBIN_SOCKETS   the rrQueue as above, the pull taking the control list first.
  *
  * Not covered: the loopback relay (unlimited, every packet local), the pcap and tracker side
  * effects of networkinterface_pop, and the CPU-delay model (host.rs:708-735), as the inbound
@@ -723,6 +746,10 @@ shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_tim
 /* QDiscMode (configuration.rs:396-397) */
 #define SHD_QDISC_FIFO 0
 #define SHD_QDISC_ROUND_ROBIN 1
+/* the same two over sockets with a control and a data buffer (socket.c:432-437): the discipline
+ * | 4.  (2 and 3 name nothing and stay SHD_ERR_INVALID.) */
+#define SHD_QDISC_FIFO_SOCKETS 4
+#define SHD_QDISC_ROUND_ROBIN_SOCKETS 5
 
 /* (Re)create n_hosts empty queues of up to `capacity` packets each, Idle relays and full
  * buckets; host h's global id (what a packet's dst is compared with) is first_host + h.  The tb_*
@@ -733,8 +760,10 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
                               const uint64_t* tb_refill_interval_ns, const uint64_t* tb_last_refill);
 /* shd_outbound_setup with the discipline named.  qdisc = SHD_QDISC_FIFO: shd_outbound_setup,
  * max_sockets is ignored.  qdisc = SHD_QDISC_ROUND_ROBIN: `capacity` is still the packets a host
- * may have queued, max_sockets the sockets it may have in its rrQueue at once.  SHD_ERR_INVALID:
- * any other qdisc, or max_sockets == 0 under round-robin (the stage stays as it was). */
+ * may have queued, max_sockets the sockets it may have in its rrQueue at once.
+ * SHD_QDISC_FIFO_SOCKETS, SHD_QDISC_ROUND_ROBIN_SOCKETS: the same two limits, max_sockets the
+ * sockets in the host's heap or rrQueue.  SHD_ERR_INVALID: any other qdisc, or max_sockets == 0
+ * under any discipline but SHD_QDISC_FIFO (the stage stays as it was). */
 shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_host, uint32_t capacity,
                                     uint32_t qdisc, uint32_t max_sockets, const uint64_t* tb_capacity,
                                     const uint64_t* tb_refill_increment, const uint64_t* tb_refill_interval_ns,
@@ -769,6 +798,15 @@ shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t fir
  * shd_outbound_setup; also where the reference panics (a time before a bucket's last refill).  A
  * NULL array with n_offers > 0 or a window_end below the previous one is SHD_ERR_INVALID before
  * anything runs.
+ *
+ * shd_outbound_advance_sockets is the same call with one more column, d_sock[k] = the canonical
+ * handle of the socket that offers packet k (compared for equality only); shd_outbound_advance is
+ * shd_outbound_advance_sockets with d_sock = NULL.  Under SHD_QDISC_FIFO_SOCKETS and
+ * SHD_QDISC_ROUND_ROBIN_SOCKETS d_prio is the packet priority (0: a control packet) and d_sock is
+ * needed: NULL with n_offers > 0 is SHD_ERR_INVALID before anything runs.  Their input contract
+ * has no priority rule -- any priorities, equal ones included -- and keeps the rest: times, sizes,
+ * packet ids, at most `capacity` packets and max_sockets sockets queued on a host, with the same
+ * consequences.  Under SHD_QDISC_FIFO and SHD_QDISC_ROUND_ROBIN d_sock is ignored.
  */
 shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
                                 const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
@@ -777,6 +815,14 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
                                 shd_batch* d_batch_out, const uint32_t** sent_pkt,
                                 const uint32_t** loc_off, const uint32_t** loc_pkt, const uint64_t** loc_time,
                                 uint64_t* n_local, uint64_t* n_stored, uint64_t* next_task_time);
+shd_status shd_outbound_advance_sockets(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                        const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                        const uint32_t* d_payload, const uint32_t* d_dst, const uint32_t* d_pkt,
+                                        uint64_t n_offers, uint64_t window_end, uint64_t bootstrap_end,
+                                        shd_batch* d_batch_out, const uint32_t** sent_pkt,
+                                        const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                        const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                        uint64_t* next_task_time);
 /* The total sizes of the last advance's batch (device, engine-owned, valid until the next advance):
  * d_size[i] = the size the offer of batch entry i carried -- with *sent_pkt what shd_ledger_record
  * keeps for the destination side.  NULL before the first advance.  SHD_ERR_STATE wherever
@@ -784,7 +830,8 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
 shd_status shd_outbound_sent_sizes(shd_ctx* ctx, const uint32_t** d_size);
 /* One host's state (any pointer may be NULL): *task_time UINT64_MAX = Idle; the cached packet;
  * the packets queued and the one the next pop takes (FIFO: the lowest priority; round-robin: the
- * head socket's first; UINT32_MAX: empty); the
+ * head socket's first; the socket disciplines: the head packet, control first, of the heap's root
+ * or the rrQueue's head socket; UINT32_MAX: empty); the
  * bucket in the struct of shd_tb_get_state (pending_until = the task time, 0 when Idle).
  * SHD_ERR_STATE while the stage is not ready -- before shd_outbound_setup, or after a contract
  * error until the next setup, as the advance; SHD_ERR_INVALID: host >= n_hosts. */
@@ -792,10 +839,11 @@ shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_ti
                                   uint32_t* cached_pkt, uint32_t* cached_size, uint32_t* queue_len,
                                   uint32_t* head_pkt, shd_tb_state* bucket);
 /* One host's rrQueue in order: handles[i] / counts[i] = the i-th socket's canonical handle and
- * its queued packets, at most `cap` entries written (host arrays; NULL with cap = 0);
- * *n_sockets = the sockets queued.  The cached packet's socket is listed only if it has further
- * packets.  SHD_ERR_STATE under FIFO, and wherever shd_outbound_get_state returns it;
- * SHD_ERR_INVALID: host >= n_hosts. */
+ * its queued packets (control plus data), at most `cap` entries written (host arrays; NULL with
+ * cap = 0); *n_sockets = the sockets queued.  Under SHD_QDISC_FIFO_SOCKETS the sockets come as
+ * the heap array in index order -- the state the send order is a function of.  The cached packet's
+ * socket is listed only if it has further packets.  SHD_ERR_STATE under SHD_QDISC_FIFO, and
+ * wherever shd_outbound_get_state returns it; SHD_ERR_INVALID: host >= n_hosts. */
 shd_status shd_outbound_get_sockets(shd_ctx* ctx, uint32_t host, uint64_t* handles, uint32_t* counts, uint32_t cap,
                                     uint32_t* n_sockets);
 
@@ -937,6 +985,20 @@ shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t*
                             uint64_t* n_batch, uint64_t* n_events, const uint32_t** loc_off,
                             const uint32_t** loc_pkt, const uint64_t** loc_time, uint64_t* n_local,
                             uint64_t* n_stored, uint64_t* outbound_next_task, uint64_t* min_deliver);
+/* shd_window_close with the offers' socket column (shd_outbound_advance_sockets); shd_window_close
+ * is this call with d_sock = NULL.  Over an outbound stage set up with one of the two socket
+ * disciplines a NULL d_sock with n_offers > 0 is SHD_ERR_INVALID before anything runs; under a
+ * communicator it is one of the preconditions the ranks agree on, so every rank's close returns
+ * it and nothing has run anywhere. */
+shd_status shd_window_close_sockets(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                    const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                    const uint32_t* d_payload, const uint32_t* d_dst, const uint32_t* d_pkt,
+                                    uint64_t n_offers, uint64_t window_end, uint64_t sim_end,
+                                    uint64_t bootstrap_end, const uint32_t** sent_pkt,
+                                    const uint8_t** sent_status, uint64_t* n_batch, uint64_t* n_events,
+                                    const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                    const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                    uint64_t* outbound_next_task, uint64_t* min_deliver);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

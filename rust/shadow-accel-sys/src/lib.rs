@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 8;
+pub const SHD_ABI_VERSION: u32 = 9;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -26,6 +26,8 @@ pub const SHD_INBOUND_FORWARDED: u32 = 1;
 pub const SHD_INBOUND_DROPPED: u32 = 2;
 pub const SHD_QDISC_FIFO: u32 = 0;
 pub const SHD_QDISC_ROUND_ROBIN: u32 = 1;
+pub const SHD_QDISC_FIFO_SOCKETS: u32 = 4;
+pub const SHD_QDISC_ROUND_ROBIN_SOCKETS: u32 = 5;
 pub const SHD_OK: shd_status = 0;
 pub const SHD_ERR_NO_EDGE: shd_status = 1;
 pub const SHD_ERR_MULTI_EDGE: shd_status = 2;
@@ -235,6 +237,7 @@ extern "C" {
     pub fn shd_outbound_setup(ctx: *mut shd_ctx, n_hosts: u32, first_host: u32, capacity: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
     pub fn shd_outbound_setup_qdisc(ctx: *mut shd_ctx, n_hosts: u32, first_host: u32, capacity: u32, qdisc: u32, max_sockets: u32, tb_capacity: *const u64, tb_refill_increment: *const u64, tb_refill_interval_ns: *const u64, tb_last_refill: *const u64) -> shd_status;
     pub fn shd_outbound_advance(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, bootstrap_end: u64, d_batch_out: *mut shd_batch, sent_pkt: *mut *const u32, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
+    pub fn shd_outbound_advance_sockets(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_sock: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, bootstrap_end: u64, d_batch_out: *mut shd_batch, sent_pkt: *mut *const u32, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, next_task_time: *mut u64) -> shd_status;
     pub fn shd_outbound_sent_sizes(ctx: *mut shd_ctx, d_size: *mut *const u32) -> shd_status;
     pub fn shd_outbound_get_state(ctx: *mut shd_ctx, host: u32, task_time: *mut u64, has_cached: *mut u32, cached_pkt: *mut u32, cached_size: *mut u32, queue_len: *mut u32, head_pkt: *mut u32, bucket: *mut shd_tb_state) -> shd_status;
     pub fn shd_outbound_get_sockets(ctx: *mut shd_ctx, host: u32, handles: *mut u64, counts: *mut u32, cap: u32, n_sockets: *mut u32) -> shd_status;
@@ -245,6 +248,7 @@ extern "C" {
     pub fn shd_ledger_stats(ctx: *mut shd_ctx, live_batches: *mut u64, live_events: *mut u64, entries_held: *mut u64, oldest_batch: *mut u64) -> shd_status;
     pub fn shd_window_open(ctx: *mut shd_ctx, window_end: u64, bootstrap_end: u64, out_off: *mut *const u32, out_pkt: *mut *const u32, out_time: *mut *const u64, out_kind: *mut *const u8, n_out: *mut u64, n_stored: *mut u64, inbound_next_task: *mut u64, n_popped: *mut u64, n_pending: *mut u64, queue_next_time: *mut u64) -> shd_status;
     pub fn shd_window_close(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, sim_end: u64, bootstrap_end: u64, sent_pkt: *mut *const u32, sent_status: *mut *const u8, n_batch: *mut u64, n_events: *mut u64, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, outbound_next_task: *mut u64, min_deliver: *mut u64) -> shd_status;
+    pub fn shd_window_close_sockets(ctx: *mut shd_ctx, d_off: *const u32, d_time: *const u64, d_prio: *const u64, d_sock: *const u64, d_size: *const u32, d_payload: *const u32, d_dst: *const u32, d_pkt: *const u32, n_offers: u64, window_end: u64, sim_end: u64, bootstrap_end: u64, sent_pkt: *mut *const u32, sent_status: *mut *const u8, n_batch: *mut u64, n_events: *mut u64, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, outbound_next_task: *mut u64, min_deliver: *mut u64) -> shd_status;
     pub fn shd_gml_parse(text: *const c_char, len: usize, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_load(path: *const c_char, xz: i32, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_graph(g: *const shd_gml, view: *mut shd_graph) -> shd_status;

@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "OK", 1: "NO_EDGE", 2: "MULTI_EDGE", 3: "UNREACHABLE", 4: "LA
 ROUTE_SHORTEST, ROUTE_DIRECT = 0, 1
 ALGO_AUTO, ALGO_SSSP, ALGO_PRUNED, ALGO_DELTA, ALGO_BLOCKED = 0, 1, 2, 3, 4
 PKT_SKIPPED, PKT_DROPPED, PKT_SENT = 0, 1, 2
-QDISC_FIFO, QDISC_ROUND_ROBIN = 0, 1
+QDISC_FIFO, QDISC_ROUND_ROBIN, QDISC_FIFO_SOCKETS, QDISC_ROUND_ROBIN_SOCKETS = 0, 1, 4, 5
 
 EXPORTED = [
     "shd_version", "shd_status_str", "shd_open", "shd_close", "shd_set_stream",
@@ -45,6 +45,7 @@ EXPORTED = [
     "shd_outbound_setup_qdisc", "shd_outbound_get_sockets",
     "shd_equeue_next_batch", "shd_ledger_setup", "shd_ledger_record", "shd_ledger_gather", "shd_ledger_stats",
     "shd_window_open", "shd_window_close", "shd_ledger_record_sharded",
+    "shd_outbound_advance_sockets", "shd_window_close_sockets",
 ]
 COMM_ID_BYTES = 128
 
@@ -234,6 +235,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_inbound_get_state": (I32, [P, U32, P, P, P, P, P, P]),
         "shd_outbound_setup": (I32, [P, U32, U32, U32, P, P, P, P]),
         "shd_outbound_advance": (I32, [P, P, P, P, P, P, P, P, U64, U64, U64, P, P, P, P, P, P, P, P]),
+        "shd_outbound_advance_sockets": (I32, [P, P, P, P, P, P, P, P, P, U64, U64, U64, P, P, P, P, P, P, P, P]),
         "shd_outbound_get_state": (I32, [P, U32, P, P, P, P, P, P, P]),
         "shd_outbound_sent_sizes": (I32, [P, P]),
         "shd_outbound_setup_qdisc": (I32, [P, U32, U32, U32, U32, U32, P, P, P, P]),
@@ -246,6 +248,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_ledger_stats": (I32, [P, P, P, P, P]),
         "shd_window_open": (I32, [P, U64, U64, P, P, P, P, P, P, P, P, P, P]),
         "shd_window_close": (I32, [P, P, P, P, P, P, P, P, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, P]),
+        "shd_window_close_sockets": (I32, [P, P, P, P, P, P, P, P, P, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P,
+                                           P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

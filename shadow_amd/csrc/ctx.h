@@ -154,6 +154,7 @@ struct OutboundState {
     DevBuf ring;                   // FIFO: OutPkt ring of `cap` slots per host, sorted by priority: all but the first packet;
                                    // round-robin: the RrSlot pool of `cap` slots per host (rr_queue.h)
     DevBuf socks, rr_words;        // round-robin: RrSock ring of max_sockets entries per host; the pool's bump count and free list
+                                   // the socket disciplines (sock_queue.h): ring is the SqSlot pool, socks the SqSock array
     DevBuf tb;                     // TbRelay per host
     DevBuf rl;                     // OutRelay per host: task time, the queue's first packet, ring head / count, the cached packet
     DevBuf cnt, nsent, nloc;       // [n_hosts + 1] record region bounds -> offsets; SENT / LOCAL records written
@@ -164,7 +165,8 @@ struct OutboundState {
     ScanScratch scan;
     uint32_t n_hosts = 0, first_host = 0, cap = 0;
     uint32_t max_sockets = 0;      // round-robin: sockets a host may have queued at once
-    bool round_robin = false;      // the discipline (SHD_QDISC_*) the stage was set up with
+    uint32_t qdisc = 0;            // the discipline (SHD_QDISC_*) the stage was set up with
+    bool with_sockets() const { return (qdisc & 4u) != 0; }   // the two disciplines whose offers carry the socket column
     uint64_t n_stored = 0;         // packets queued or cached after the last advance
     uint64_t prev_end = 0;         // the last advance's window_end
     bool advanced = false;         // an advance has run since the setup (b_* hold its batch)

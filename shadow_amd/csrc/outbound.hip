@@ -14,7 +14,8 @@
 //     :235-273 _networkinterface_selectRoundRobin, :366-392 networkinterface_wantsSend: the
 //              rrQueue (rr_queue.h restates both)
 //   src/main/host/network/network_queuing_disciplines.c
-//     :90-102  the FIFO comparison of two sockets' head priorities (never equal)
+//     :90-102  the FIFO comparison of two sockets' head priorities (never equal under OutFifo's
+//              contract; a tie is "smaller" both ways: OutFifoSock)
 //   src/main/network/relay/mod.rs
 //     :110-135 notify: Idle -> forward_later(ZERO), a task at the offer's time ("allow packets to
 //              accumulate", :124-126); Pending -> nothing
@@ -50,8 +51,14 @@
 // offers at one instant belong to one event (one accumulation under relay/mod.rs:124-126) or to
 // one socket.  Two events on one host at the same nanosecond that offer on different sockets are
 // rotated together here; in the reference the first event's task may already have drained its
-// packets.  Within a socket packets leave in offer order: the separate control buffer
-// (socket.c:467) is not modelled.
+// packets.  Within a socket packets leave in offer order under OutFifo and OutRr, which see a
+// socket as one list.  OutFifoSock and OutRrSock (below, sock_queue.h) keep the sockets with the
+// control and the data buffer of socket.c:432-437 -- every TCP control packet has priority 0 and
+// leaves before its socket's data -- and, for FIFO, the reference's array heap of sockets
+// (priority_queue.c), whose send order is a function of the array: a control packet offered to a
+// queued socket changes its key in place.  Under OutFifoSock a same-instant retransmission is
+// exact too (order within a socket is offer order); two events of one host at one nanosecond
+// stay inexact as under round-robin.
 //
 // Not covered: the loopback relay (unlimited, every packet local), the pcap and tracker side
 // effects of networkinterface_pop, and the CPU-delay model (as the inbound stage).
@@ -71,6 +78,7 @@
 #include "ctx.h"
 #include "rr_queue.h"
 #include "scan.h"
+#include "sock_queue.h"
 #include "tbucket_ops.h"
 
 namespace shd {
@@ -85,6 +93,8 @@ constexpr uint32_t kOutNoPkt = ~0u;    // not a packet id
 constexpr uint32_t kOutBatch = 8;
 constexpr uint32_t kOutLanes = 64;
 static_assert(kOutBatch * 32 * kOutLanes <= 65536 && kOutLanes % 64 == 0, "outb_run's static LDS");
+// (the socket disciplines park one more 8-byte column, the offering socket: 40 bytes an offer, 20 KB)
+static_assert(kOutBatch * 40 * kOutLanes <= 65536, "outb_run's static LDS with the socket column");
 constexpr int kOutPinWord = 81;        // ctx->h_pin words [81, 86)
 constexpr int kOutWords = 5;           // status, n_sent, n_local, n_stored, min task time
 static_assert(kOutPinWord > kPinMarker && kOutPinWord + kOutWords <= kPinWords,
@@ -98,7 +108,7 @@ constexpr uint32_t kOutPanic = 16u;     // where the reference panics (token_buc
 constexpr uint32_t kOutSpin = 32u;      // the task budget ran out (unreachable under the input contract)
 constexpr uint32_t kOutRegion = 64u;    // a record past the host's region (unreachable: one record per packet)
 constexpr uint32_t kOutBadPrio = 128u;  // a priority equal to one still queued on the host (FIFO)
-constexpr uint32_t kOutSockFull = 256u; // one socket more than max_sockets in a host's rrQueue (round-robin)
+constexpr uint32_t kOutSockFull = 256u; // one socket more than max_sockets in a host's rrQueue (round-robin) or heap
 
 struct OutPkt {   // 24 bytes: a queued packet
     uint64_t prio;
@@ -266,6 +276,91 @@ struct OutRr {
     }
 };
 
+// The two disciplines over sockets with both buffers of socket.c (SHD_QDISC_FIFO_SOCKETS,
+// SHD_QDISC_ROUND_ROBIN_SOCKETS): sock_queue.h's queue, the functions tests/sock_queue_main.cpp
+// compiles.  An offer has two keys, the packet's priority (0: a control packet) and the offering
+// socket's canonical handle, a column of its own (Args::sock); priorities need not be unique.  The
+// queue's words live in the relay words -- count: the packets queued; pad: the entries in the
+// socket array (0 with count 1: the one packet lies in head_prio (its socket), tail_prio (its
+// priority) and head_*); otherwise head: the rrQueue's start, tail_prio: the pool's bump count and
+// free list -- so outb_count serves all four.  R.head_pkt is current only for a queue of one:
+// shd_outbound_get_state reads the arrays.
+template <bool kFifo>
+struct OutSock {
+    struct Args {
+        SqSlot* pool_all;
+        SqSock* socks_all;
+        const uint64_t* sock;   // the offers' socket column
+        uint32_t cap, max_sockets;
+    };
+    SqQueue q;
+    SqSlot* pool;
+    SqSock* socks;
+    uint32_t cap, max_sockets;
+    static __host__ __device__ __forceinline__ void unpack(const OutRelay& R, SqQueue& q) {
+        q.count = R.count;
+        q.n_socks = R.pad;
+        q.ring_head = R.head;
+        q.pkt = R.head_pkt;
+        q.size = R.head_size;
+        q.payload = R.head_payload;
+        q.dst = R.head_dst;
+        if (R.pad) {
+            q.handle = q.prio = 0;
+            q.bump = (uint32_t)R.tail_prio;
+            q.free = (uint32_t)(R.tail_prio >> 32);
+        } else {
+            q.handle = R.head_prio;
+            q.prio = R.tail_prio;
+            q.bump = 0;
+            q.free = kSqNil;
+        }
+    }
+    __device__ __forceinline__ OutSock(const Args& a, uint32_t h, const OutRelay& R)
+        : pool(a.pool_all + (size_t)h * a.cap), socks(a.socks_all + (size_t)h * a.max_sockets), cap(a.cap),
+          max_sockets(a.max_sockets) {
+        unpack(R, q);
+    }
+    __device__ __forceinline__ uint32_t insert(OutRelay& R, const OutPkt& e, uint64_t handle) {
+        const SqOffer o = sq_offer(q, pool, cap, socks, max_sockets, kFifo, handle, e.prio, e.pkt, e.size, e.payload, e.dst);
+        if (o != kSqOk) return o == kSqPoolFull ? kOutRingFull : kOutSockFull;
+        R.count = q.count;   // (the one word the kernel's own code reads between the calls)
+        return 0;
+    }
+    __device__ __forceinline__ void pop(OutRelay& R, uint32_t& p_, uint32_t& s_, uint32_t& pl_, uint32_t& d_) {
+        sq_pop(q, pool, socks, max_sockets, kFifo, p_, s_, pl_, d_);
+        R.count = q.count;
+    }
+    __device__ __forceinline__ void store(OutRelay& R) {
+        R.count = q.count;
+        R.pad = q.n_socks;
+        R.head = q.ring_head;
+        R.head_pkt = q.pkt;
+        R.head_size = q.size;
+        R.head_payload = q.payload;
+        R.head_dst = q.dst;
+        if (q.n_socks) {
+            R.head_prio = 0;
+            R.tail_prio = (uint64_t)q.bump | ((uint64_t)q.free << 32);
+        } else {
+            R.head_prio = q.handle;
+            R.tail_prio = q.prio;
+        }
+    }
+};
+using OutFifoSock = OutSock<true>;
+using OutRrSock = OutSock<false>;
+
+// a discipline whose offers carry the socket column beside the priority
+template <class Q> struct OutHasSock { static constexpr bool value = false; };
+template <bool kFifo> struct OutHasSock<OutSock<kFifo>> { static constexpr bool value = true; };
+
+// the socket column of the offer batch: LDS only in the instances that call this
+__device__ __forceinline__ uint64_t (*outb_sock_col())[kOutLanes] {
+    __shared__ uint64_t s_sk[kOutBatch][kOutLanes];
+    return s_sk;
+}
+
 // cnt[h] = the records host h can write: its offers + queued + cached; cnt[n_hosts] = 0 (the scan's
 // total).  Offsets that are not a CSR over n_offers offers are reported and count as no offers.
 __global__ __launch_bounds__(256) void outb_count(uint32_t n_hosts, const uint32_t* __restrict__ off,
@@ -302,6 +397,9 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
     __shared__ uint64_t s_tm[kOutBatch][kOutLanes], s_pr[kOutBatch][kOutLanes];
     __shared__ uint32_t s_sz[kOutBatch][kOutLanes], s_pl[kOutBatch][kOutLanes], s_ds[kOutBatch][kOutLanes],
         s_pk[kOutBatch][kOutLanes];
+    constexpr bool kSock = OutHasSock<Q>::value;
+    uint64_t(*s_sk)[kOutLanes] = nullptr;
+    if constexpr (kSock) s_sk = outb_sock_col();
     const uint32_t h = blockIdx.x * kOutLanes + threadIdx.x;
     uint32_t* status = reinterpret_cast<uint32_t*>(words);
     bool live = h < n_hosts;
@@ -337,11 +435,13 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
             if (have && bi == kOutBatch) {
                 uint64_t tm[kOutBatch], pr[kOutBatch];
                 uint32_t sz[kOutBatch], pl[kOutBatch], ds[kOutBatch], pk[kOutBatch];
+                [[maybe_unused]] uint64_t sk[kSock ? kOutBatch : 1];
 #pragma unroll
                 for (uint32_t i = 0; i < kOutBatch; ++i) {
                     const uint32_t kk = min(k + i, ke - 1);
                     tm[i] = time[kk];
                     pr[i] = prio[kk];
+                    if constexpr (kSock) sk[i] = qa.sock[kk];
                     sz[i] = size[kk];
                     pl[i] = payload[kk];
                     ds[i] = dst[kk];
@@ -355,6 +455,7 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
                     s_pl[i][threadIdx.x] = pl[i];
                     s_ds[i][threadIdx.x] = ds[i];
                     s_pk[i][threadIdx.x] = pk[i];
+                    if constexpr (kSock) s_sk[i][threadIdx.x] = sk[i];
                 }
                 bi = 0;
             }
@@ -376,9 +477,16 @@ __global__ __launch_bounds__(kOutLanes) void outb_run(
                     err |= kOutBadPkt;
                     break;
                 }
-                if (const uint32_t refused = q.insert(R, e)) {
-                    err |= refused;
-                    break;
+                if constexpr (kSock) {
+                    if (const uint32_t refused = q.insert(R, e, s_sk[bi][threadIdx.x])) {
+                        err |= refused;
+                        break;
+                    }
+                } else {
+                    if (const uint32_t refused = q.insert(R, e)) {
+                        err |= refused;
+                        break;
+                    }
                 }
                 last_t = t_of;
                 if (R.task == kOutIdle) R.task = t_of;   // Relay::notify: forward_later(ZERO)
@@ -521,10 +629,13 @@ shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t fir
                                     const uint64_t* tb_refill_increment, const uint64_t* tb_refill_interval_ns,
                                     const uint64_t* tb_last_refill) {
     if (!ctx || capacity == 0) return SHD_ERR_INVALID;
-    if (qdisc != SHD_QDISC_FIFO && qdisc != SHD_QDISC_ROUND_ROBIN) return SHD_ERR_INVALID;
+    if (qdisc != SHD_QDISC_FIFO && qdisc != SHD_QDISC_ROUND_ROBIN && qdisc != SHD_QDISC_FIFO_SOCKETS &&
+        qdisc != SHD_QDISC_ROUND_ROBIN_SOCKETS)
+        return SHD_ERR_INVALID;
     const bool rr = qdisc == SHD_QDISC_ROUND_ROBIN;
+    const bool sq = qdisc == SHD_QDISC_FIFO_SOCKETS || qdisc == SHD_QDISC_ROUND_ROBIN_SOCKETS;
     // (slot and ring indices are summed in 32 bits before they wrap)
-    if (rr && (max_sockets == 0 || max_sockets > 0x7FFFFFFFu || capacity > 0x7FFFFFFFu)) return SHD_ERR_INVALID;
+    if ((rr || sq) && (max_sockets == 0 || max_sockets > 0x7FFFFFFFu || capacity > 0x7FFFFFFFu)) return SHD_ERR_INVALID;
     if ((uint64_t)first_host + n_hosts > 0xFFFFFFFFull) return SHD_ERR_INVALID;   // global ids are u32
     std::vector<TbRelay> hb;
     SHD_TRY(tb_rows(n_hosts, tb_capacity, tb_refill_increment, tb_refill_interval_ns, tb_last_refill, hb));
@@ -533,7 +644,10 @@ shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t fir
     hipStream_t s = ctx->stream;
     SHD_HIP(hipSetDevice(ctx->device));
     const size_t n1 = std::max<size_t>(n_hosts, 1);
-    SHD_TRY(O.ring.ensure(std::max<size_t>((size_t)n_hosts * capacity, 1) * (rr ? sizeof(RrSlot) : sizeof(OutPkt))));
+    SHD_TRY(O.ring.ensure(std::max<size_t>((size_t)n_hosts * capacity, 1) *
+                          (sq ? sizeof(SqSlot) : rr ? sizeof(RrSlot) : sizeof(OutPkt))));
+    // (the socket disciplines' pool words lie in the relay words: neither array needs a first write)
+    if (sq) SHD_TRY(O.socks.ensure(std::max<size_t>((size_t)n_hosts * max_sockets, 1) * sizeof(SqSock)));
     if (rr) {
         SHD_TRY(O.socks.ensure(std::max<size_t>((size_t)n_hosts * max_sockets, 1) * sizeof(RrSock)));
         SHD_TRY(O.rr_words.ensure(n1 * sizeof(uint2)));
@@ -563,8 +677,8 @@ shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t fir
     O.n_hosts = n_hosts;
     O.first_host = first_host;
     O.cap = capacity;
-    O.round_robin = rr;
-    O.max_sockets = rr ? max_sockets : 0;
+    O.qdisc = qdisc;
+    O.max_sockets = rr || sq ? max_sockets : 0;
     O.n_stored = 0;
     O.prev_end = 0;
     O.advanced = false;
@@ -579,18 +693,19 @@ shd_status shd_outbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t first_hos
                                     tb_refill_increment, tb_refill_interval_ns, tb_last_refill);
 }
 
-shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
-                                const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
-                                const uint32_t* d_dst, const uint32_t* d_pkt, uint64_t n_offers,
-                                uint64_t window_end, uint64_t bootstrap_end, shd_batch* d_batch_out,
-                                const uint32_t** sent_pkt, const uint32_t** loc_off, const uint32_t** loc_pkt,
-                                const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
-                                uint64_t* next_task_time) {
+shd_status shd_outbound_advance_sockets(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                        const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                        const uint32_t* d_payload, const uint32_t* d_dst, const uint32_t* d_pkt,
+                                        uint64_t n_offers, uint64_t window_end, uint64_t bootstrap_end,
+                                        shd_batch* d_batch_out, const uint32_t** sent_pkt, const uint32_t** loc_off,
+                                        const uint32_t** loc_pkt, const uint64_t** loc_time, uint64_t* n_local,
+                                        uint64_t* n_stored, uint64_t* next_task_time) {
     if (!ctx) return SHD_ERR_INVALID;
     OutboundState& O = ctx->outb;
     if (!O.ready) return SHD_ERR_STATE;
     // argument errors: nothing has run, the stage stays as it was
     if (n_offers && (!d_off || !d_time || !d_prio || !d_size || !d_payload || !d_dst || !d_pkt)) return SHD_ERR_INVALID;
+    if (n_offers && O.with_sockets() && !d_sock) return SHD_ERR_INVALID;   // (the plain disciplines never read it)
     if (n_offers && O.n_hosts == 0) return SHD_ERR_INVALID;
     if (window_end < O.prev_end) return SHD_ERR_INVALID;
     const uint64_t n_slots = n_offers + O.n_stored;   // every packet leaves at most once
@@ -631,7 +746,11 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
                 O.r_dst.as<uint32_t>(), O.r_pay.as<uint32_t>(), O.r_size.as<uint32_t>(), O.prev_end, window_end,
                 bootstrap_end, words);
         };
-        if (O.round_robin)
+        if (O.with_sockets()) {
+            const OutFifoSock::Args qa{O.ring.as<SqSlot>(), O.socks.as<SqSock>(), d_sock, O.cap, O.max_sockets};
+            if (O.qdisc == SHD_QDISC_FIFO_SOCKETS) run(outb_run<OutFifoSock>, qa);
+            else run(outb_run<OutRrSock>, OutRrSock::Args{qa.pool_all, qa.socks_all, qa.sock, qa.cap, qa.max_sockets});
+        } else if (O.qdisc == SHD_QDISC_ROUND_ROBIN)
             run(outb_run<OutRr>, OutRr::Args{O.ring.as<RrSlot>(), O.socks.as<RrSock>(), O.rr_words.as<uint2>(), O.cap,
                                              O.max_sockets});
         else
@@ -680,6 +799,18 @@ shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint6
     return SHD_OK;
 }
 
+shd_status shd_outbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
+                                const uint32_t* d_dst, const uint32_t* d_pkt, uint64_t n_offers,
+                                uint64_t window_end, uint64_t bootstrap_end, shd_batch* d_batch_out,
+                                const uint32_t** sent_pkt, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                uint64_t* next_task_time) {
+    return shd_outbound_advance_sockets(ctx, d_off, d_time, d_prio, nullptr, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                        window_end, bootstrap_end, d_batch_out, sent_pkt, loc_off, loc_pkt, loc_time,
+                                        n_local, n_stored, next_task_time);
+}
+
 shd_status shd_outbound_sent_sizes(shd_ctx* ctx, const uint32_t** d_size) {
     if (!ctx || !d_size) return SHD_ERR_INVALID;
     OutboundState& O = ctx->outb;
@@ -704,7 +835,22 @@ shd_status shd_outbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_ti
     if (cached_pkt) *cached_pkt = r.has_cached ? r.cached_pkt : 0;
     if (cached_size) *cached_size = r.has_cached ? r.cached_size : 0;
     if (queue_len) *queue_len = r.count;
-    if (head_pkt) *head_pkt = r.count ? r.head_pkt : kOutNoPkt;
+    if (head_pkt) {
+        *head_pkt = r.count ? r.head_pkt : kOutNoPkt;
+        if (O.with_sockets() && r.count && r.pad) {   // the head socket's entry, then its head packet's slot
+            const bool fifo = O.qdisc == SHD_QDISC_FIFO_SOCKETS;
+            SqQueue q;
+            OutFifoSock::unpack(r, q);
+            SqSock e;
+            SqSlot p;
+            SHD_HIP(hipMemcpy(&e, O.socks.as<SqSock>() + (size_t)host * O.max_sockets + sq_at(q, 0, O.max_sockets, fifo),
+                              sizeof(e), hipMemcpyDeviceToHost));
+            const uint32_t slot = e.cfirst != kSqNil ? e.cfirst : e.dfirst;
+            if (slot >= O.cap) return SHD_ERR_STATE;   // (never after a window that returned SHD_OK)
+            SHD_HIP(hipMemcpy(&p, O.ring.as<SqSlot>() + (size_t)host * O.cap + slot, sizeof(p), hipMemcpyDeviceToHost));
+            *head_pkt = p.pkt;
+        }
+    }
     if (bucket) {
         TbRelay b;
         SHD_HIP(hipMemcpy(&b, O.tb.as<TbRelay>() + host, sizeof(b), hipMemcpyDeviceToHost));
@@ -722,9 +868,26 @@ shd_status shd_outbound_get_sockets(shd_ctx* ctx, uint32_t host, uint64_t* handl
                                     uint32_t* n_sockets) {
     if (!ctx) return SHD_ERR_INVALID;
     OutboundState& O = ctx->outb;
-    if (!O.ready || !O.round_robin) return SHD_ERR_STATE;   // (a FIFO stage has no rrQueue)
+    if (!O.ready || O.qdisc == SHD_QDISC_FIFO) return SHD_ERR_STATE;   // (a plain FIFO stage keeps no sockets)
     if (host >= O.n_hosts || (cap && (!handles || !counts))) return SHD_ERR_INVALID;
     SHD_HIP(hipSetDevice(ctx->device));
+    if (O.with_sockets()) {   // the host's words, its pool and its socket array, listed by sock_queue.h
+        OutRelay r;
+        std::vector<SqSlot> pool(O.cap);
+        std::vector<SqSock> socks(O.max_sockets);
+        SHD_HIP(hipMemcpy(&r, O.rl.as<OutRelay>() + host, sizeof(r), hipMemcpyDeviceToHost));
+        SHD_HIP(hipMemcpy(pool.data(), O.ring.as<SqSlot>() + (size_t)host * O.cap, pool.size() * sizeof(SqSlot),
+                          hipMemcpyDeviceToHost));
+        SHD_HIP(hipMemcpy(socks.data(), O.socks.as<SqSock>() + (size_t)host * O.max_sockets,
+                          socks.size() * sizeof(SqSock), hipMemcpyDeviceToHost));
+        SqQueue q;
+        OutFifoSock::unpack(r, q);
+        if (q.n_socks > O.max_sockets) return SHD_ERR_STATE;   // (never after a window that returned SHD_OK)
+        const uint32_t n = sq_counts(q, pool.data(), O.cap, socks.data(), O.max_sockets,
+                                     O.qdisc == SHD_QDISC_FIFO_SOCKETS, handles, counts, cap);
+        if (n_sockets) *n_sockets = n;
+        return SHD_OK;
+    }
     // the host's words, its pool and its socket ring; the chains are walked here by rr_queue.h
     OutRelay r;
     uint2 w;

@@ -1,7 +1,7 @@
 // One host's round-robin queuing discipline (network_interface.c:235-273, :366-392;
 // network_queuing_disciplines.c:29-88): the rrQueue, an ordered list of distinct sockets, each
 // with the packets it has offered in offer order (socket.c:434-467; the separate control buffer of
-// socket.c:467 is not modelled).  One set of functions for the kernel (outbound.hip) and for a
+// socket.c:467 is sock_queue.h's, for SHD_QDISC_ROUND_ROBIN_SOCKETS).  One set of functions for the kernel (outbound.hip) and for a
 // program of its own (tests/rr_queue_main.cpp, built with the sanitizers): free of HIP.
 //
 //   offer   the packet goes behind its socket's packets; a socket that is not queued is pushed at

@@ -54,7 +54,8 @@ static shd_status window_no_off(shd_ctx* ctx) {
 // whatever happens locally -- the precondition agreement, the sharded round (its own status
 // agreement carries an outbound failure: the round then commits nowhere), the sharded record.
 static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
-                                       const uint64_t* d_prio, const uint32_t* d_size, const uint32_t* d_payload,
+                                       const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                       const uint32_t* d_payload,
                                        const uint32_t* d_dst, const uint32_t* d_pkt, uint64_t n_offers,
                                        uint64_t window_end, uint64_t sim_end, uint64_t bootstrap_end,
                                        const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
@@ -70,6 +71,7 @@ static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, cons
     if (!window_ready(ctx) || !W.opened) pre = SHD_ERR_STATE;
     else if (window_end != W.window_end) pre = SHD_ERR_INVALID;
     else if (n_own && B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) pre = SHD_ERR_INVALID;
+    else if (n_own && n_offers && ctx->outb.with_sockets() && !d_sock) pre = SHD_ERR_INVALID;   // the socket column
     else if (!n_own) pre = window_no_off(ctx);
     SHD_TRY(comm_agree(ctx, pre));
     W.opened = false;
@@ -79,9 +81,9 @@ static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, cons
     const uint32_t *b_pkt = nullptr, *b_size = nullptr;
     shd_status st = SHD_OK;
     if (n_own) {
-        st = shd_outbound_advance(ctx, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
-                                  bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local, n_stored,
-                                  outbound_next_task);
+        st = shd_outbound_advance_sockets(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                          window_end, bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time,
+                                          n_local, n_stored, outbound_next_task);
         if (st == SHD_OK && batch.n_packets) st = shd_outbound_sent_sizes(ctx, &b_size);
         if (st == SHD_OK && batch.n_packets) st = W.status.ensure(batch.n_packets);
     } else {
@@ -164,20 +166,21 @@ shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap
     return SHD_OK;
 }
 
-shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time, const uint64_t* d_prio,
-                            const uint32_t* d_size, const uint32_t* d_payload, const uint32_t* d_dst,
-                            const uint32_t* d_pkt, uint64_t n_offers, uint64_t window_end, uint64_t sim_end,
-                            uint64_t bootstrap_end, const uint32_t** sent_pkt, const uint8_t** sent_status,
-                            uint64_t* n_batch, uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
-                            const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
-                            uint64_t* outbound_next_task, uint64_t* min_deliver) {
+shd_status shd_window_close_sockets(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                    const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                    const uint32_t* d_payload, const uint32_t* d_dst, const uint32_t* d_pkt,
+                                    uint64_t n_offers, uint64_t window_end, uint64_t sim_end, uint64_t bootstrap_end,
+                                    const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
+                                    uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                    const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                    uint64_t* outbound_next_task, uint64_t* min_deliver) {
     if (!ctx) return SHD_ERR_INVALID;
     WindowState& W = ctx->win;
     if (window_sharded(ctx)) {
         // the one refusal without a collective: a relay not set up under this communicator (every
         // rank sets it up, or none); everything else is agreed between the ranks first
         if (!ctx->relay.ready || !ctx->relay.sharded) return SHD_ERR_STATE;
-        return window_close_sharded(ctx, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
+        return window_close_sharded(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
                                     sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off, loc_pkt,
                                     loc_time, n_local, n_stored, outbound_next_task, min_deliver);
     }
@@ -188,9 +191,9 @@ shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t*
     if (B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) return SHD_ERR_INVALID;
     shd_batch batch{};
     const uint32_t* b_pkt = nullptr;
-    SHD_TRY(shd_outbound_advance(ctx, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
-                                 bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local, n_stored,
-                                 outbound_next_task));
+    SHD_TRY(shd_outbound_advance_sockets(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                         window_end, bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local,
+                                         n_stored, outbound_next_task));
     W.opened = false;
     W.has_out = false;
     uint64_t sent = 0, low = ~0ull;
@@ -217,6 +220,18 @@ shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t*
     if (n_events) *n_events = sent;
     if (min_deliver) *min_deliver = low;
     return SHD_OK;
+}
+
+shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time, const uint64_t* d_prio,
+                            const uint32_t* d_size, const uint32_t* d_payload, const uint32_t* d_dst,
+                            const uint32_t* d_pkt, uint64_t n_offers, uint64_t window_end, uint64_t sim_end,
+                            uint64_t bootstrap_end, const uint32_t** sent_pkt, const uint8_t** sent_status,
+                            uint64_t* n_batch, uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                            const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                            uint64_t* outbound_next_task, uint64_t* min_deliver) {
+    return shd_window_close_sockets(ctx, d_off, d_time, d_prio, nullptr, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                    window_end, sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off,
+                                    loc_pkt, loc_time, n_local, n_stored, outbound_next_task, min_deliver);
 }
 
 }  // extern "C"

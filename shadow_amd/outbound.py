@@ -10,6 +10,11 @@ priority (``network_interface.c:276-316``), ``Relay::forward_until_blocked``
 ``qdisc="round-robin"`` the interface keeps the rrQueue instead (``network_interface.c:235-273``,
 ``:366-392``): the sockets that have packets queued take turns, one packet each, and the per-offer
 key is the offering socket's canonical handle (``sock=`` where FIFO takes ``prio=``).
+``qdisc="fifo-sockets"`` and ``"round-robin-sockets"`` are the two disciplines over sockets with
+both buffers of ``socket.c:432-437``: a packet of priority 0 (every TCP control packet) goes to its
+socket's control list, which is pulled first, and under ``"fifo-sockets"`` the sockets stand in the
+reference's array heap (``priority_queue.c``).  An offer then has both columns, ``prio=`` and
+``sock=``, and priorities need not be unique.
 
 ``OutboundStage(engine, capacity, refill_increment, refill_interval, last_refill, first_host=0,
 qdisc="fifo", max_sockets=64)`` -- bucket parameters per host, all three 0 for a host without a bucket; host ``h``'s global id is
@@ -31,7 +36,9 @@ from .tbucket import SIM_START, create_token_bucket
 
 IDLE = 2**64 - 1
 NO_PKT = 2**32 - 1
-QDISC = {"fifo": N.QDISC_FIFO, "round-robin": N.QDISC_ROUND_ROBIN}
+QDISC = {"fifo": N.QDISC_FIFO, "round-robin": N.QDISC_ROUND_ROBIN, "fifo-sockets": N.QDISC_FIFO_SOCKETS,
+         "round-robin-sockets": N.QDISC_ROUND_ROBIN_SOCKETS}
+SOCKET_QDISCS = ("fifo-sockets", "round-robin-sockets")   # an offer is (priority, socket): two columns
 
 
 @dataclass
@@ -76,8 +83,8 @@ class Sent:
 class OutboundStage:
     def __init__(self, engine, capacity, refill_increment, refill_interval, last_refill=SIM_START,
                  first_host: int = 0, ring_capacity: int = 4096, qdisc: str = "fifo", max_sockets: int = 64):
-        """``ring_capacity``: the packets a host may have queued; ``max_sockets`` (round-robin
-        only): the sockets it may have in its rrQueue at once."""
+        """``ring_capacity``: the packets a host may have queued; ``max_sockets`` (every discipline
+        but ``"fifo"``): the sockets it may have in its rrQueue or heap at once."""
         if qdisc not in QDISC:
             raise ValueError(f"qdisc must be one of {sorted(QDISC)}, not {qdisc!r}")
         self.eng = engine
@@ -104,18 +111,21 @@ class OutboundStage:
         return cls(engine, cap, inc, itv, start, first_host, ring_capacity, qdisc, max_sockets)
 
     def advance_device(self, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers: int,
-                       window_end: int, bootstrap_end: int = 0) -> DeviceBatch:
+                       window_end: int, bootstrap_end: int = 0, d_sock=None) -> DeviceBatch:
         """Device pointers (ints, ctypes pointers or torch tensors; all None for no offers).
         ``d_prio`` is the discipline's 64-bit key per offer: the packet priority under FIFO, the
-        socket's canonical handle under round-robin."""
+        socket's canonical handle under round-robin.  The two socket disciplines take the packet
+        priority (0: control) in ``d_prio`` and the socket's canonical handle in ``d_sock``; the
+        other two ignore ``d_sock``."""
         as_p = lambda a: a if a is None or isinstance(a, (int, C.c_void_p)) else N.ptr(a)  # noqa: E731
         b = N.Batch()
         sp, lo, lp, lt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         n_local, n_stored, nxt = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        N.check(self.eng.lib.shd_outbound_advance(
-            self.eng.ctx, as_p(d_off), as_p(d_time), as_p(d_prio), as_p(d_size), as_p(d_payload), as_p(d_dst),
-            as_p(d_pkt), int(n_offers), int(window_end), int(bootstrap_end), C.byref(b), C.byref(sp), C.byref(lo),
-            C.byref(lp), C.byref(lt), C.byref(n_local), C.byref(n_stored), C.byref(nxt)), "shd_outbound_advance")
+        N.check(self.eng.lib.shd_outbound_advance_sockets(
+            self.eng.ctx, as_p(d_off), as_p(d_time), as_p(d_prio), as_p(d_sock), as_p(d_size), as_p(d_payload),
+            as_p(d_dst), as_p(d_pkt), int(n_offers), int(window_end), int(bootstrap_end), C.byref(b), C.byref(sp),
+            C.byref(lo), C.byref(lp), C.byref(lt), C.byref(n_local), C.byref(n_stored), C.byref(nxt)),
+            "shd_outbound_advance")
         return DeviceBatch(b, sp.value, lo.value, lp.value, lt.value, b.n_packets, n_local.value, n_stored.value,
                            nxt.value)
 
@@ -123,8 +133,13 @@ class OutboundStage:
                 window_end: int, bootstrap_end: int = 0, sock=None) -> Sent:
         """Host arrays of one window's offers grouped by host (or none) -> host copies.  ``sock``
         (the offering sockets' canonical handles) is the round-robin spelling of ``prio``: the
-        same column; giving both is an error."""
-        if sock is not None:
+        same column; giving both is an error.  Under the two socket disciplines ``prio`` and
+        ``sock`` are two columns and both are given."""
+        d_sock = None
+        if self.qdisc in SOCKET_QDISCS:
+            if off is not None and (prio is None or sock is None):
+                raise ValueError(f"qdisc {self.qdisc!r} takes both prio and sock")
+        elif sock is not None:
             if prio is not None:
                 raise ValueError("prio and sock name the same column: give one")
             prio = sock
@@ -137,9 +152,12 @@ class OutboundStage:
             keep = [dev(off, np.uint32, np.int32), dev(time, np.uint64, np.int64), dev(prio, np.uint64, np.int64)] + \
                    [dev(a, np.uint32, np.int32) for a in (size, payload, dst, pkt)]
             assert len(keep[0]) == self.n_hosts + 1 and all(len(k) == n for k in keep[1:])
+            if self.qdisc in SOCKET_QDISCS:
+                d_sock = dev(sock, np.uint64, np.int64)
+                assert len(d_sock) == n
             torch.cuda.synchronize()
-        out = self.advance_device(*keep, n, window_end, bootstrap_end)
-        del keep
+        out = self.advance_device(*keep, n, window_end, bootstrap_end, d_sock)
+        del keep, d_sock
         return self.sent(out)
 
     def sent(self, out: DeviceBatch) -> Sent:
@@ -157,7 +175,9 @@ class OutboundStage:
         return Sent(src_off, t, d, p, sp, loc_off, lp, lt, out.n_stored, out.next_task_time)
 
     def sockets(self, host: int) -> list:
-        """One host's rrQueue in order: ``[(handle, queued packets), ...]``.  Round-robin only."""
+        """One host's queued sockets: ``[(handle, queued packets), ...]`` -- in rrQueue order under
+        the round-robin disciplines, the heap array in index order under ``"fifo-sockets"``.  Not
+        under ``"fifo"``."""
         hd, cn = np.zeros(self.max_sockets, np.uint64), np.zeros(self.max_sockets, np.uint32)
         n = C.c_uint32(0)
         N.check(self.eng.lib.shd_outbound_get_sockets(self.eng.ctx, int(host), N.ptr(hd), N.ptr(cn), len(hd),

@@ -87,14 +87,16 @@ class Window:
         return Opened(rec, n_pop.value, n_pend.value, qn.value)
 
     def close(self, d_off, d_time, d_prio, d_size, d_payload, d_dst, d_pkt, n_offers: int, window_end: int,
-              sim_end: int, bootstrap_end: int = 0) -> Closed:
-        """The offers as device pointers (ints, ctypes pointers or torch tensors; all None for none)."""
+              sim_end: int, bootstrap_end: int = 0, d_sock=None) -> Closed:
+        """The offers as device pointers (ints, ctypes pointers or torch tensors; all None for none).
+        ``d_sock``: the offering sockets' canonical handles, the column an outbound stage with
+        ``qdisc="fifo-sockets"`` or ``"round-robin-sockets"`` needs beside ``d_prio``."""
         sp, ss, lo, lp, lt = (C.c_void_p() for _ in range(5))
         n_batch, n_ev, n_local, n_stored, nxt, md = (C.c_uint64(0) for _ in range(6))
-        N.check(self.eng.lib.shd_window_close(
-            self.eng.ctx, _as_p(d_off), _as_p(d_time), _as_p(d_prio), _as_p(d_size), _as_p(d_payload), _as_p(d_dst),
-            _as_p(d_pkt), int(n_offers), int(window_end), int(sim_end), int(bootstrap_end), C.byref(sp), C.byref(ss),
-            C.byref(n_batch), C.byref(n_ev), C.byref(lo), C.byref(lp), C.byref(lt), C.byref(n_local),
+        N.check(self.eng.lib.shd_window_close_sockets(
+            self.eng.ctx, _as_p(d_off), _as_p(d_time), _as_p(d_prio), _as_p(d_sock), _as_p(d_size), _as_p(d_payload),
+            _as_p(d_dst), _as_p(d_pkt), int(n_offers), int(window_end), int(sim_end), int(bootstrap_end), C.byref(sp),
+            C.byref(ss), C.byref(n_batch), C.byref(n_ev), C.byref(lo), C.byref(lp), C.byref(lt), C.byref(n_local),
             C.byref(n_stored), C.byref(nxt), C.byref(md)), "shd_window_close")
         return Closed(sp.value, ss.value, lo.value, lp.value, lt.value, n_batch.value, n_ev.value, n_local.value,
                       n_stored.value, nxt.value, md.value)
