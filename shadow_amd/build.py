@@ -10,7 +10,10 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("routing.hip", "blocked.hip", "relay.hip", "relay_radix.hip", "relay_wide.hip",
+# (the slowest units first, so the parallel build starts them first)
+SRC = [os.path.join(HERE, "csrc", f) for f in ("routing_sssp_lds.hip", "relay.hip", "routing_sssp_global.hip",
+                                                "routing_prune.hip", "routing.hip", "routing_wide.hip",
+                                                "blocked.hip", "relay_radix.hip", "relay_wide.hip",
                                                 "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue.hip",
                                                 "hosts.cpp", "rounds.hip", "flush.hip", "inbound.hip",

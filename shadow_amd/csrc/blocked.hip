@@ -12,7 +12,7 @@
 //    never applied to it.  Dijkstra's loss label is the minimum LEFT fold over the
 //    shortest-latency walks; every arc (u,v) on such a walk satisfies D[s][u] + w == D[s][v] and
 //    hence w == D[u][v] (a "globally tight" arc).  The loss pass keeps exactly those arcs and
-//    runs the label-correcting kernel (sssp_lds_group, routing.hip) with every label seeded at
+//    runs the label-correcting kernel (sssp_lds_group, routing_sssp_lds.hip) with every label seeded at
 //    (D[s][v], +inf loss): it only appends one arc on the right at a time, and a label can only
 //    improve through a tight arc, so it converges to Dijkstra's loss bits.
 //

@@ -1,4 +1,4 @@
-"""Plain numpy restatement of the fused dense prune (nearest_rows + prune_fused in routing.hip).
+"""Plain numpy restatement of the fused dense prune (nearest_rows + prune_fused in routing_prune.hip).
 
 The rules, for a graph given as a dense latency matrix W (W[x, y]: the smallest latency of an arc
 x -> y in ns, INF where there is none; the diagonal is INF, self-loops are no arcs here):

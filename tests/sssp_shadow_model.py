@@ -1,4 +1,4 @@
-"""CPU model of the dense SSSP's fire-and-forget sweeps (sssp_lds_shadow, shadow_amd/csrc/routing.hip).
+"""CPU model of the dense SSSP's fire-and-forget sweeps (sssp_lds_shadow, shadow_amd/csrc/routing_sssp_lds.hip).
 
 A plain restatement of the sweep rule, with none of the kernel's machinery:
 

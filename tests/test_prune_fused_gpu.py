@@ -1,4 +1,4 @@
-"""GPU tests of the fused dense prune (nearest_rows + prune_fused, the default when SHD_PRUNE_K = 32,
+"""GPU tests of the fused dense prune (nearest_rows + prune_fused, the default when
 the default shape and stage 2 are on).  Every case compares the whole table, latency and loss bits,
 with the C restatement (corc.routing), and `arcs_kept` with the numpy model's count
 (tests/prune_fused_model.py): the kept set is a function of the graph alone."""

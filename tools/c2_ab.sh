@@ -2,7 +2,7 @@
 # C2 build timing only (bench routing leg), alternating an environment toggle for an A/B of
 # build-path changes: AB_VAR=NAME tools/c2_ab.sh [v1 v2 ...]  (default 0 1; each value twice, alternating)
 cd "$(dirname "$0")/.."
-var=${AB_VAR:-SHD_FLAGS_DMA}
+var=${AB_VAR:-SHD_SSSP_SHADOW}
 vals=("$@"); [ ${#vals[@]} -eq 0 ] && vals=(0 1)
 for v in "${vals[@]}" "${vals[@]}"; do
   env "$var=$v" timeout -k 10 120 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-relay \

@@ -1,7 +1,9 @@
 """Phase breakdown of the SSSP kernels on a BA graph (C4 rows: global labels; C3: LDS labels),
 from a tuning build with -DSHD_SSSP_PROF.
 
-Build:  tools/build_prof.sh SHD_SSSP_PROF routing.hip tools/libshd_sssp_prof.so
+Build:  tools/build_prof.sh SHD_SSSP_PROF routing_sssp_global.hip tools/libshd_sssp_prof.so
+        (the c3 graph runs the LDS-label kernel: build routing_sssp_lds.hip under the macro instead;
+        each unit has its own counters and hook, and the tool reads the one its graph runs)
 Run:    SHD_ACCEL_LIB=tools/libshd_sssp_prof.so python tools/c4_prof.py [rows] [c4|c3] [algo]
 """
 import ctypes as C
@@ -25,11 +27,12 @@ lat = torch.empty((rows, n), dtype=torch.int64, device="cuda")
 loss = torch.empty((rows, n), dtype=torch.float32, device="cuda")
 lib = C.CDLL(_native.LIB_PATH)
 out = (C.c_ulonglong * 8)()
+prof = lib.shd_debug_sssp_global_prof if graph == "c4" else lib.shd_debug_sssp_prof
 run_rows(eng, algo, 0, rows, lat, loss)
-assert lib.shd_debug_sssp_prof(out, 1) == 0
+assert prof(out, 1) == 0
 run_rows(eng, algo, 0, rows, lat, loss)
 torch.cuda.synchronize()
-assert lib.shd_debug_sssp_prof(out, 0) == 0
+assert prof(out, 0) == 0
 rw = out[7]   # (row, wave) pairs
 print(f"rows={rows} row-waves={rw} sweeps/row={out[5] / max(rw, 1):.2f} expanded/row-wave={out[6] / max(rw, 1):.1f} "
       f"ms_main={eng.last_info()['ms_main']:.3f}")

@@ -1,8 +1,10 @@
+# SQ counters of the C2 build's LDS-label SSSP kernel (sssp_lds_shadow by default, sssp_lds_group
+# with SHD_SSSP_SHADOW=0), one --pmc pass per counter set
 out=gpurun_out/pmc_sssp; mkdir -p $out
 i=0
 for ctrs in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS" \
   "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE GRBM_COUNT" \
   "SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_INSTS_FLAT" ; do
   i=$((i+1))
-  SHD_SSSP_NR=1 timeout -s KILL 120 rocprofv3 --pmc $ctrs --kernel-include-regex sssp_lds_group --output-format csv -d $out/p$i -o run -- python bench.py --no-cpu-baseline --no-c3 --no-c4 --no-relay --steps 3 --warmup 1 > $out/p$i.log 2>&1 || { echo "pass $i failed"; tail -3 $out/p$i.log; exit 1; }
+  timeout -s KILL 120 rocprofv3 --pmc $ctrs --kernel-include-regex "sssp_lds_(shadow|group)" --output-format csv -d $out/p$i -o run -- python bench.py --no-cpu-baseline --no-c3 --no-c4 --no-relay --steps 3 --warmup 1 > $out/p$i.log 2>&1 || { echo "pass $i failed"; tail -3 $out/p$i.log; exit 1; }
 done

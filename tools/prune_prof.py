@@ -1,6 +1,6 @@
 """Per-workgroup phase timeline of prune_rows on C2 (tuning build with -DSHD_SSSP_PROF).
 
-Build:  tools/build_prof.sh SHD_SSSP_PROF routing.hip tools/libshd_sssp_prof.so
+Build:  tools/build_prof.sh SHD_SSSP_PROF routing_prune.hip tools/libshd_sssp_prof.so
 Run:    SHD_ACCEL_LIB=tools/libshd_sssp_prof.so python tools/prune_prof.py [shape ...]
 Per shape (SHD_PRUNE_SHAPE): shader clocks per phase (median over workgroups, thread 0) and the
 100 MHz start/end timeline of the workgroups relative to the first start.

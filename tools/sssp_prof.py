@@ -1,6 +1,6 @@
 """Phase breakdown of the padded-list SSSP kernel (C2; tuning build with -DSHD_SSSP_PROF).
 
-Build:  tools/build_prof.sh SHD_SSSP_PROF routing.hip tools/libshd_sssp_prof.so
+Build:  tools/build_prof.sh SHD_SSSP_PROF routing_sssp_lds.hip tools/libshd_sssp_prof.so
 Run:    SHD_ACCEL_LIB=tools/libshd_sssp_prof.so python tools/sssp_prof.py [builds]
 Prints shader clocks per phase summed over waves, per wave and row (one wave's share of a row).
 """
