@@ -11,9 +11,10 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 # (the slowest units first, so the parallel build starts them first)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("routing_sssp_lds.hip", "relay.hip", "routing_sssp_global.hip",
-                                                "routing_prune.hip", "routing.hip", "routing_wide.hip",
-                                                "blocked.hip", "relay_radix.hip", "relay_wide.hip",
+SRC = [os.path.join(HERE, "csrc", f) for f in ("routing_sssp_lds.hip", "relay_stamp.hip", "relay_bins.hip",
+                                                "routing_sssp_global.hip", "routing_prune.hip",
+                                                "routing.hip", "relay_shard.hip", "routing_wide.hip",
+                                                "blocked.hip", "relay_radix.hip", "relay_wide.hip", "relay.hip",
                                                 "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue.hip",
                                                 "hosts.cpp", "rounds.hip", "flush.hip", "inbound.hip",

@@ -321,7 +321,7 @@ void round_note(shd_ctx* ctx, uint64_t min_deliver, uint64_t min_latency);
 // the smallest / largest of n device words (rounds.hip); one host synchronisation
 shd_status min_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
 shd_status max_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out);
-// shd_relay_round_sharded with the caller's own status on entry (relay.hip): a failure is carried
+// shd_relay_round_sharded with the caller's own status on entry (relay_shard.hip): a failure is carried
 // into the round's status agreement -- the local pipeline is skipped, the round commits nowhere
 shd_status relay_round_sharded_local(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o,
                                      shd_status local);

@@ -25,11 +25,16 @@
 //      24-byte events exchanged and merged per destination (reported as the local pipeline)
 // Units -- every kernel is defined in one unit and launched only there; another unit reaches it
 // through a host function declared below:
-//   relay.hip         3 7 8   K0 and the K1 stamps; pipeline 7's histograms, scans and K4; the sharded
-//                             rounds; the ladder over the pipelines, the commit, the C entry points
+//   relay_stamp.hip   3 7 8   K0 and the K1 stamps (by packet for 3, into the bins for 7 and 8)
+//   relay_bins.hip    7 8     pipeline 7's histograms, scans and K4 (for 8 over gathered records)
+//   relay_shard.hip   8       the sharded rounds: the bins exchanged, and the packing path
 //   relay_radix.hip   3       K2-K4 of the radix back end
 //   relay_wide.hip    1       the 64-bit pipeline
+//   relay.hip                 the ladder over the pipelines, the commit, the C entry points
+// relay_bins.h holds the limits and the bin arithmetic that several of them compile.
 #pragma once
+#include <algorithm>
+
 #include "ctx.h"
 #include "wave.h"
 
@@ -77,7 +82,7 @@ __device__ __forceinline__ bool draw_drops(uint32_t h, double reliability, bool&
     return (uint64_t)h >= th + (low ? 1u : 0u);
 }
 
-// The narrow pipelines' arguments (relay.hip, relay_radix.hip)
+// The narrow pipelines' arguments (relay_stamp.hip, relay_bins.hip, relay_radix.hip)
 struct RelayArgs3 {
     uint32_t n_hosts, n_nodes;
     uint32_t src_lo, n_src;    // source hosts of this context: [src_lo, src_lo + n_src)
@@ -115,17 +120,67 @@ struct RelayArgs3 {
     uint64_t sh_mul;
 };
 
+// The bins of a sharded round (relay_round_sharded_v7): rank r's destinations [r * per, ...)
+// start bin r * bpr; n_bins over all ranks
+struct XShard {
+    uint32_t per = 0, bpr = 0, n_bins = 0;
+    uint64_t mul = 0;
+    uint32_t first_bin(uint32_t r) const { return std::min<uint32_t>(r * bpr, n_bins); }
+};
+
+// K4 of a sharded round (relay_round_sharded_v7, bin_sort_v7<true>): bin j of this rank's own bins takes
+// its records from every sender's received slice: sender q's records of the bin start at
+// rbase[q] + sc[q * stride + fb + j] - sc[q * stride + fb] (sc: the senders' exclusive bin scans
+// from the gathered sizing rows).  Packet indices are per sender; the sort key uses the global
+// packet order (the senders' batches back to back, pbase[q] = packets of the senders before q),
+// which is (src host, event id) order because the senders own increasing source ranges.
+struct XSrc {
+    uint32_t world, me, fb, stride, kq;
+    const uint32_t* sc;
+    const uint32_t* rbase;   // sender q's slice in the received records (q != me)
+    const uint32_t* pbase;
+    const uint4* own;        // this rank's own records stay where its stamp put them (never exchanged)
+    const uint64_t* rst;     // [world] the status each sender carried into the exchange (own: own_st)
+    uint32_t own_st;
+};
+
 // relay.hip
 RelayArgs3 relay_args3(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
+// the pending launch error, then the round's reductions into R.red_host (one host sync)
+shd_status relay_read_red(shd_ctx* ctx);
+// the ladder over the local pipelines (nothing of the hosts' state committed), and the commit
+shd_status relay_run(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
+shd_status relay_commit(shd_ctx* ctx, shd_relay_out* o);
+// shd_relay_flush (flush.hip): one round on the batch it grouped on the device
+shd_status relay_flush_round(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
+
+// relay_stamp.hip
 // K0 (no launch when the batch carries chances or the CPU's draws) and the stamp that writes the
 // records by packet (pipeline 3)
 void relay_launch_draws(shd_ctx* ctx, const RelayArgs3& a);
 void relay_launch_stamp(shd_ctx* ctx, const RelayArgs3& a);
-// the pending launch error, then the round's reductions into R.red_host (one host sync)
-shd_status relay_read_red(shd_ctx* ctx);
-// shd_relay_flush (flush.hip): one round on the batch it grouped on the device; under a
-// communicator on this rank's grouped sends, with the CPU's draws
-shd_status relay_flush_round(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
+// the stamp that places the records into their bins (pipelines 7, 8): G workgroups, lds dynamic bytes
+void relay_launch_stamp_bins(shd_ctx* ctx, const RelayArgs3& a, uint32_t G, size_t lds);
+// that stamp's static LDS bytes (0: the query failed), its sends per chunk, and relay_stamp_v6's
+// LDS besides the host -> node map (shd_relay_setup: does the map fit)
+size_t relay_stamp_bins_static_lds();
+uint32_t relay_stamp_chunk();
+uint32_t relay_stamp_fixed_lds();
+
+// relay_bins.hip
+bool relay_v7_ok(shd_ctx* ctx, uint64_t n, uint32_t n_bins);
+XShard xshard(uint32_t H, uint32_t world);
+// v7 up to and including the stamp; with xsh (a sharded round) the records stay in their bins
+// for the exchange (no bin sort, no read-back), else the bin sort and the reductions' read-back
+shd_status relay_device_v7(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o,
+                           const XShard* xsh = nullptr);
+// K4 of a sharded round over this rank's nb bins and n_own destinations, into R.m_*; without
+// bins only the event count and the agreed status are written
+void relay_launch_bin_sort_x(shd_ctx* ctx, uint32_t n_own, uint32_t nb, uint64_t round_end, const XSrc& xs);
+
+// relay_shard.hip
+shd_status relay_shard_alloc(shd_ctx* ctx);   // buffers sized by the host count and the ranks (shd_relay_setup)
+// shd_relay_flush under a communicator (flush.hip): this rank's grouped sends, the CPU's draws
 shd_status relay_flush_round_sharded(shd_ctx* ctx, const shd_batch* b, const shd_round* rd, shd_relay_out* o);
 
 // relay_wide.hip, relay_radix.hip: one pipeline attempt each

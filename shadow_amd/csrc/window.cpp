@@ -7,7 +7,7 @@
 // open is local as before, the close a collective -- the sharded round, then the sharded record,
 // which brings each sent packet's (size, id) to the rank that owns its destination.
 // The stages are the ones the separate calls drive (equeue.hip, ledger.hip, inbound.hip,
-// outbound.hip, relay.hip); this file only chains them and keeps what lies between two calls.
+// outbound.hip, relay*.hip); this file only chains them and keeps what lies between two calls.
 #include "ctx.h"
 
 using namespace shd;

@@ -1,6 +1,6 @@
 """Shape-sweep parity of the relay stamp (worker.rs:361-411 restated by corc.relay_round).
 
-The stamp kernel (relay.hip relay_stamp_v6) walks host groups in source-node order; each group
+The stamp kernel (relay_stamp.hip relay_stamp_v6) walks host groups in source-node order; each group
 stages its source nodes' path rows in LDS when they fit (rows x n_nodes <= 2048 entries) and,
 when a workgroup walks more than one group, prefetches the next group's rows while the current
 one runs.  Round 4 shipped an out-of-bounds LDS index in that prefetch (a next group spanning
@@ -16,7 +16,7 @@ from tests.test_comm_gpu import _check_rank, _run_ranks, _slice_batch
 
 pytestmark = pytest.mark.gpu
 
-N_CU = 256            # MI355X compute units: the stamp's persistent grid (relay.hip relay_device_v7)
+N_CU = 256            # MI355X compute units: the stamp's persistent grid (relay_bins.hip relay_device_v7)
 ROW_LDS = 2048        # kS5RowLds: staged path-table entries per group
 GROUP_SENDS = 4096    # kS6Cap: v7_group_size's default sends per group
 
@@ -49,7 +49,7 @@ def _batch(H, per_host, seed, start, span, same_instant=False):
 
 
 def _group_size(n_src, G, n, S=GROUP_SENDS):
-    """relay.hip v7_group_size (S = the RELAY_GROUP_SENDS knob)."""
+    """relay_bins.hip v7_group_size (S = the RELAY_GROUP_SENDS knob)."""
     if not S or not n or not n_src or not G:
         return 64
     want = int(min(64.0, max(8.0, S / (n / n_src))))

@@ -1,6 +1,6 @@
 """Per-wave timeline of the relay's K0 draws (tuning build with -DSHD_STAMP_PROF).
 
-Build:  tools/build_prof.sh SHD_STAMP_PROF relay.hip tools/libshd_k0prof.so
+Build:  tools/build_prof.sh SHD_STAMP_PROF relay_stamp.hip tools/libshd_k0prof.so
 Run:    SHD_ACCEL_LIB=tools/libshd_k0prof.so python tools/k0_prof.py
 Prints the waves' start spread, lifetimes (100 MHz clock) and shader clocks per phase.
 """

@@ -1,6 +1,6 @@
 """Phase breakdown of relay_stamp_v6 (tuning build with -DSHD_STAMP_PROF).
 
-Build:  hipcc <build.py FLAGS> -DSHD_STAMP_PROF <SRC> -o tools/libshd_prof.so
+Build:  tools/build_prof.sh SHD_STAMP_PROF relay_stamp.hip tools/libshd_prof.so
 Run:    SHD_ACCEL_LIB=tools/libshd_prof.so python tools/stamp_prof.py [rounds]
 Prints shader clocks per phase summed over workgroups, per round and per workgroup.
 """
