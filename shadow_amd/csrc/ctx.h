@@ -74,15 +74,12 @@ struct CodelState {   // CoDel router queues (codel.hip)
     bool ready = false;
 };
 
-// Stored runs of the event queues before they are compacted (the limit, SHD_EQ_MAX_RUNS knob,
-// may be set lower, down to 2).  Each advance merges one source per run, each compaction half
+// Stored runs of the event queues before they are compacted (the EQ_MAX_RUNS knob may set the
+// limit lower, down to 2).  Each advance merges one source per run, each compaction half
 // the runs: on C5 (24 rounds at the steady ~41M pending events) the advance averaged 0.370 ms
 // at 8 runs, 0.359 at 12 and 0.355 at 15 (a compaction every ~3 / ~6 / ~7 rounds against more
 // sources in every pass); 12 keeps the count kernel's lanes to 13 of its 16.
-#ifndef SHD_EQ_MAX_RUNS
-#define SHD_EQ_MAX_RUNS 12   // (tuning builds: tools/build_variant.sh -DSHD_EQ_MAX_RUNS=n, n <= 15)
-#endif
-constexpr int kEqMaxRuns = SHD_EQ_MAX_RUNS;
+constexpr int kEqMaxRuns = 12;
 constexpr int kEqSlots = kEqMaxRuns + 2;   // + the compaction target + a batch slot handed out for adoption
 
 struct EqRunBuf {   // one stored run of the event queues: a CSR of per-host sorted events
@@ -95,7 +92,7 @@ struct EqRunBuf {   // one stored run of the event queues: a CSR of per-host sor
     bool live = false;
 };
 
-struct EqState {   // destination event queues (equeue.hip): a list of sorted runs (one per batch)
+struct EqState {   // destination event queues (equeue_priv.h): a list of sorted runs (one per batch)
     EqRunBuf run[kEqSlots];         // slots
     int lend = -1;                  // the slot handed out by shd_equeue_batch_buffers (not live yet)
     bool fold_next = false;         // the next pass folds a compaction in (the run limit was reached)
@@ -104,7 +101,7 @@ struct EqState {   // destination event queues (equeue.hip): a list of sorted ru
     DevBuf curs[2];                 // [kEqSlots][n_hosts] u32 cursors (first unpopped), double-buffered
     DevBuf bcut;                    // [n_hosts] the batch's first kept event per host
     DevBuf pd, ps, pq, pt;          // the last call's popped events
-    DevBuf pop_cnt, keep_cnt, pop_off, next, left;
+    DevBuf pop_cnt, keep_cnt, pop_off, next;
     DevBuf ranges;                  // [n_hosts][kEqMaxRuns + 1] (cursor, cut) pairs of the last count
     int ccur = 0;
     uint32_t n_hosts = 0;           // queues held here: all hosts, or a sharded rank's [host_lo, host_lo + n_hosts)

@@ -17,9 +17,9 @@ namespace shd {
     X(SSSP_G) X(SSSP_BLOCK) X(SSSP_SLOTS) X(SSSP_RESERVE) X(FW_TILE) X(SSSP_REORDER)            \
     X(SSSP_NO_SPREAD) X(SSSP_GLOBAL) X(SSSP_DELTA) X(SSSP_STATS) X(SPIN_WAIT) X(SSSP_SHADOW)    \
     X(PRUNE_DENSE_BUILD) X(PRUNE_STAGE2) X(SYNC_KERNEL)                                         \
-    X(EQ_COUNT_BLOCKS) X(EQ_WAVE_MERGE) X(EQ_SEARCH_ONLY) X(EQ_MAX_RUNS) X(RELAY_GROUP_SENDS) X(HIST_SCALAR) X(RELAY_FORCE_V1)         \
+    X(EQ_SEARCH_ONLY) X(EQ_MAX_RUNS) X(RELAY_GROUP_SENDS) X(HIST_SCALAR) X(RELAY_FORCE_V1)      \
     X(RELAY_FORCE_V3) X(RELAY_NO_LDS_MAP) X(SHARD_CHUNK_ROWS) X(SHARD_REPLICATE_MB)             \
-    X(SHARD_RESERVE_SLOTS) X(RELAY_SHARD_X24) X(FLUSH_COPY) X(PRUNE_SHAPE) X(EQ_FOLD) X(EQ_FOLD_TAKE) X(RELAY_SCAN2)   \
+    X(SHARD_RESERVE_SLOTS) X(RELAY_SHARD_X24) X(FLUSH_COPY) X(PRUNE_SHAPE) X(RELAY_SCAN2)       \
     X(LEDGER_REMAP_SEARCH) X(PRUNE_FUSED) X(TEST_FAIL)
 
 enum Knob : int {

@@ -1,11 +1,133 @@
 // Relay pipeline 3 (overview: relay_priv.h), the radix back end: the stamp's records sorted by destination
-// (scan.h), then every destination's run sorted by one wave.  The fallback of pipeline 7.
+// (radix_sort_pairs below), then every destination's run sorted by one wave.  The fallback of pipeline 7.
+//
+// radix_sort_pairs: stable LSD radix sort of (u32 key, 16-byte record) pairs, 6 bits per pass --
+// a per-tile digit histogram, one scan of the digit-major counts (scan.h), and a stable scatter
+// (each thread ranks its 16 consecutive keys, a block scan orders the tile digit-major).
 #include <algorithm>
 
 #include "relay_priv.h"
 #include "scan.h"
 
 namespace shd {
+
+constexpr uint32_t kRsT = 256, kRsK = 16, kRsTile = kRsT * kRsK;   // 4096 pairs per tile
+constexpr uint32_t kRsBits = 6, kRsDig = 1u << kRsBits;
+
+// counts[d * n_tiles + tile] = keys of the tile with digit d
+__global__ __launch_bounds__(kRsT) void rs_hist(const uint32_t* __restrict__ keys, uint64_t n, uint32_t shift,
+                                                uint32_t n_tiles, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t h[kRsDig];
+    const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+    if (tid < kRsDig) h[tid] = 0;
+    __syncthreads();
+    const uint64_t b = (uint64_t)tile * kRsTile;
+#pragma unroll 4
+    for (uint32_t j = 0; j < kRsK; ++j) {
+        const uint64_t i = b + (uint64_t)j * kRsT + tid;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & (kRsDig - 1)], 1u);
+    }
+    __syncthreads();
+    if (tid < kRsDig) counts[(size_t)tid * n_tiles + tile] = h[tid];
+}
+
+// stable scatter: thread t owns the tile's keys [t*K, t*K+K); its keys' ranks come from a
+// digit-major block scan of the per-thread digit counts (LDS, u16)
+__global__ __launch_bounds__(kRsT) void rs_scatter(const uint32_t* __restrict__ kin, const uint4* __restrict__ vin,
+                                                   uint32_t* __restrict__ kout, uint4* __restrict__ vout, uint64_t n,
+                                                   uint32_t shift, uint32_t n_tiles,
+                                                   const uint32_t* __restrict__ offs) {
+    constexpr uint32_t S = kRsT + 1;   // padded row (bank spread)
+    __shared__ uint16_t cnt[kRsDig * S];
+    __shared__ uint32_t s_part[kRsT];
+    __shared__ uint32_t s_dstart[kRsDig];
+    const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+    const uint64_t b = (uint64_t)tile * kRsTile + (uint64_t)tid * kRsK;
+    uint32_t key[kRsK], rank[kRsK];
+    for (uint32_t d = 0; d < kRsDig; ++d) cnt[d * S + tid] = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kRsK; ++j) key[j] = b + j < n ? kin[b + j] : 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t j = 0; j < kRsK; ++j) {
+        if (b + j < n) {
+            const uint32_t d = (key[j] >> shift) & (kRsDig - 1);
+            rank[j] = cnt[d * S + tid]++;
+        }
+    }
+    __syncthreads();
+    // digit-major exclusive scan over (d, t): thread x takes row d = x / 4, columns (x % 4) * 64 ..
+    const uint32_t d0 = tid >> 2, c0 = (tid & 3) * 64;
+    uint32_t sum = 0;
+    for (uint32_t c = 0; c < 64; ++c) sum += cnt[d0 * S + c0 + c];
+    s_part[tid] = sum;
+    __syncthreads();
+    if (tid < 64) {   // one wave scans the 256 partial sums (4 per lane)
+        uint32_t p[4], t = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            p[i] = s_part[tid * 4 + i];
+            t += p[i];
+        }
+        uint32_t incl = t;
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(incl, o);
+            if (tid >= o) incl += y;
+        }
+        uint32_t run = incl - t;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s_part[tid * 4 + i] = run;
+            run += p[i];
+        }
+    }
+    __syncthreads();
+    {
+        uint32_t run = s_part[tid];
+        if ((tid & 3) == 0) s_dstart[d0] = run;   // the digit's first position in the tile
+        for (uint32_t c = 0; c < 64; ++c) {
+            const uint32_t v = cnt[d0 * S + c0 + c];
+            cnt[d0 * S + c0 + c] = (uint16_t)run;
+            run += v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < kRsK; ++j) {
+        if (b + j < n) {
+            const uint32_t d = (key[j] >> shift) & (kRsDig - 1);
+            const uint32_t pos = cnt[d * S + tid] + rank[j];   // position in the digit-major tile
+            const uint64_t gp = (uint64_t)offs[(size_t)d * n_tiles + tile] + (pos - s_dstart[d]);
+            kout[gp] = key[j];
+            vout[gp] = vin[b + j];
+        }
+    }
+}
+
+// Stable sort of n (key, record) pairs by the low `bits` bits of the key, ping-ponging between
+// (k0, v0) and (k1, v1); *in_first says where the result is (true: k0 / v0).
+static shd_status radix_sort_pairs(DevBuf& counts, ScanScratch& scan, uint32_t* k0, uint4* v0, uint32_t* k1, uint4* v1, uint64_t n,
+                                   uint32_t bits, bool* in_first, hipStream_t s) {
+    *in_first = true;
+    if (n == 0) return SHD_OK;
+    const uint32_t n_tiles = (uint32_t)((n + kRsTile - 1) / kRsTile);
+    const uint64_t nc = (uint64_t)n_tiles * kRsDig;
+    SHD_TRY(counts.ensure(nc * 4 + 16));
+    uint32_t* kin = k0;
+    uint4* vin = v0;
+    uint32_t* kout = k1;
+    uint4* vout = v1;
+    for (uint32_t shift = 0; shift < bits; shift += kRsBits) {
+        rs_hist<<<n_tiles, kRsT, 0, s>>>(kin, n, shift, n_tiles, counts.as<uint32_t>());
+        SHD_HIP(hipGetLastError());
+        SHD_TRY(scan_excl2(scan, counts.as<uint32_t>(), counts.as<uint32_t>(), nullptr, nullptr, nc, s));
+        rs_scatter<<<n_tiles, kRsT, 0, s>>>(kin, vin, kout, vout, n, shift, n_tiles, counts.as<uint32_t>());
+        SHD_HIP(hipGetLastError());
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+        *in_first = !*in_first;
+    }
+    return SHD_OK;
+}
 
 // ev_off[d] = first position of destination d in the sorted keys (lower bound), d in [0, H]
 __global__ __launch_bounds__(256) void bucket_offsets(const uint32_t* __restrict__ key, uint64_t n,
@@ -230,7 +352,7 @@ shd_status relay_device_v3(shd_ctx* ctx, const shd_batch* b, const shd_round* rd
     relay_launch_draws(ctx, a);   // K0: the per-host generator streams
     relay_launch_stamp(ctx, a);
     SHD_HIP(hipGetLastError());
-    // stable LSD radix sort of the records by destination (keys <= H), hand-written (scan.h)
+    // stable LSD radix sort of the records by destination (keys <= H), hand-written
     uint32_t bits = 1;
     while (bits < 32 && (H >> bits) != 0) ++bits;
     bool first = true;

@@ -1,5 +1,5 @@
 // Wave-level exchanges and sorts shared by the relay's destination sorts (relay_*.hip) and the
-// event queues' per-host merge (equeue.hip): 64-lane gfx950 waves, keys held NPL per lane
+// event queues' per-host merge (equeue_pass.hip): 64-lane gfx950 waves, keys held NPL per lane
 // (element e = lane + 64 c).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,6 +73,21 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
         v = w < v ? w : v;
     }
     return v;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// LDS written by some lanes of the wave is read by others: the only sync a wave-private LDS row
+// needs (no workgroup barrier)
+__device__ __forceinline__ void wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Bitonic sort of 64 * NPL keys held NPL per lane (element e = lane + 64 c), ascending.

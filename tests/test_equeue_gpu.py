@@ -23,16 +23,15 @@ def _check(p, oq, H, window_end):
     assert p.next_time == (min(heads) if heads else 2**64 - 1)
 
 
-MERGE_KNOBS = {"sort": {}, "search": {"EQ_SEARCH_ONLY": 1}, "merge16": {"EQ_WAVE_MERGE": 0}}
+MERGE_KNOBS = {"sort": {}, "search": {"EQ_SEARCH_ONLY": 1}}
 
 
 @pytest.mark.parametrize("merge", list(MERGE_KNOBS))
 @pytest.mark.parametrize("chance_mode,H,P", [(False, 3000, 120_000), (True, 3000, 120_000), (False, 40, 40_000)])
 def test_queues_across_rounds_vs_oracle(engine, chance_mode, H, P, merge, knob):
-    """H=3000: ~40 popped events per host and round, some hosts past the 16-lane merge's LDS
-    stage (64); H=40: ~1000, past both stages (64 / 160), so the global-search path is the one
-    checked.  merge: eqr_merge ranking staged hosts by a wave sort (default) or by searches
-    alone, or eqr_merge16 (four hosts a wave)."""
+    """H=3000: ~40 popped events per host and round, the staged path (the merge's LDS stage holds
+    160); H=40: ~1000, past the stage, so the global-search path is the one checked.  merge:
+    eqr_merge ranking staged hosts by a wave sort (default) or by searches alone."""
     for k, v in MERGE_KNOBS[merge].items():
         knob(k, v)
     from shadow_amd import synth
