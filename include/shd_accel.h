@@ -28,6 +28,8 @@
  *                             EventQueue::push (worker.rs:619-629, core/work/event_queue.rs:28-48)
  *   shd_path_packet_counts <- RoutingInfo::increment_packet_count / log_packet_counts
  *                             (graph/mod.rs:451-474)
+ *   shd_offers_group       <- notify_socket_has_packets -> Relay::notify (relay/mod.rs:110-135), the
+ *                             staging site: the thread running the host appends the offer to its stage
  */
 #ifndef SHD_ACCEL_H
 #define SHD_ACCEL_H
@@ -39,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 9
+#define SHD_ABI_VERSION 10
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -999,6 +1001,96 @@ shd_status shd_window_close_sockets(shd_ctx* ctx, const uint32_t* d_off, const u
                                     const uint32_t** loc_off, const uint32_t** loc_pkt,
                                     const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
                                     uint64_t* outbound_next_task, uint64_t* min_deliver);
+
+/* ---------------------------------------------------------------------------------------
+ * Staged offers -> the outbound stage's device columns.  The window's offers as the worker threads
+ * leave them at the round barrier, grouped by host on the device: no CPU group-by, no split into
+ * seven arrays, no copy per array.  The staging site is notify_socket_has_packets -> Relay::notify
+ * (relay/mod.rs:110-135): the thread that runs the host appends the packet's offer to its stage.
+ *
+ * Stages (shd_relay_flush's contract; scheduler/thread_per_core.rs:188-206: a host runs on one
+ * thread per round): stage k is one thread's buffer -- stage_runs[k] runs, run r being
+ * (run_host[k][r], run_count[k][r]), and stage_offers[k] records in offers[k], run after run.  A
+ * host's offers form ONE run of consecutive records in ONE stage, in the order the host made them
+ * (time order: what shd_outbound_advance asks of a host's offers).  Stages and runs come in any
+ * order; a host without a run has no offers; a run of count 0 is allowed.  run_host holds global
+ * host ids; the hosts grouped are the outbound stage's, [first_host, first_host + n_hosts) -- under
+ * a communicator a rank stages its own hosts only (unlike shd_relay_flush, where every rank sees
+ * every stage).
+ *
+ * An offer record is offer_words consecutive uint32_t words: 8 under SHD_QDISC_FIFO /
+ * SHD_QDISC_ROUND_ROBIN, 10 under the two _SOCKETS disciplines (10 is accepted under the plain
+ * ones: the socket column is then ignored, as d_sock is):
+ *   word 0     time_off = now - time_base        word 4     pkt (the caller's id)
+ *   word 1     dst (destination HostId, global)  word 5     reserved, ignored
+ *   word 2     size (total packet size)          word 6, 7  the d_prio key, low then high
+ *   word 3     payload                           word 8, 9  d_sock, low then high (width 10 only)
+ *
+ * Outputs: engine-owned device arrays, valid until the next shd_offers_group, which
+ * shd_outbound_advance_sockets / shd_window_close_sockets take as they stand (d_time = time_base +
+ * time_off; *d_sock is NULL at width 8); *n_offers their length.  Any output pointer may be NULL.
+ * Stages in pinned memory (shd_host_alloc; every array of every stage) are read where they lie,
+ * each byte once; otherwise they are copied stage after stage (the FLUSH_COPY knob forces that).
+ * Records should be 8-byte aligned (any allocator's are); others are read word by word.
+ *
+ * Refusals -- nothing the outbound stage or the stages own has changed:
+ *   SHD_ERR_STATE    the outbound stage is not set up
+ *   SHD_ERR_NO_HOST  a run's host lies outside [first_host, first_host + n_hosts)
+ *   SHD_ERR_INVALID  a host with two runs; a stage whose run counts do not add up to its
+ *                    stage_offers; offer_words not 8 or 10, or 8 under a _SOCKETS discipline; a NULL
+ *                    array where a count is not zero; 2^32 or more offers or runs
+ * Nothing else is checked here: times, priorities, sizes and ids reach shd_outbound_advance
+ * unchanged and its contract checks apply to them.
+ * ------------------------------------------------------------------------------------- */
+shd_status shd_offers_group(shd_ctx* ctx, uint32_t n_stages, const uint32_t* stage_runs,
+                            const uint32_t** run_host, const uint32_t** run_count,
+                            const uint64_t* stage_offers, const uint32_t** offers, uint32_t offer_words,
+                            uint64_t time_base, const uint32_t** d_off, const uint64_t** d_time,
+                            const uint64_t** d_prio, const uint64_t** d_sock, const uint32_t** d_size,
+                            const uint32_t** d_payload, const uint32_t** d_dst, const uint32_t** d_pkt,
+                            uint64_t* n_offers);
+
+/* ---------------------------------------------------------------------------------------
+ * shd_window_close from staged offers: shd_offers_group, then shd_window_close_sockets on its
+ * arrays; the stage arguments are shd_offers_group's, the rest shd_window_close_sockets'.
+ * One context: the window's own preconditions come first (parts ready, the open seen, window_end
+ * its open's, room in the ledger), then the grouping; a refused grouping returns its status with
+ * the window still open and no stage run, so a corrected close may follow.
+ * Under a communicator of N > 1 ranks the grouping runs first and locally, without a collective,
+ * and its status is the rank's word in the close's precondition agreement (step 1 above): if any
+ * rank's stages are refused every rank returns the lowest failing rank's status, nothing has run
+ * anywhere and the window is still open on every rank.  The sequence of collectives is
+ * shd_window_close's.  A rank without hosts passes n_stages = 0 (a run there is SHD_ERR_NO_HOST).
+ * ------------------------------------------------------------------------------------- */
+shd_status shd_window_close_staged(shd_ctx* ctx, uint32_t n_stages, const uint32_t* stage_runs,
+                                   const uint32_t** run_host, const uint32_t** run_count,
+                                   const uint64_t* stage_offers, const uint32_t** offers, uint32_t offer_words,
+                                   uint64_t time_base, uint64_t window_end, uint64_t sim_end,
+                                   uint64_t bootstrap_end, const uint32_t** sent_pkt,
+                                   const uint8_t** sent_status, uint64_t* n_batch, uint64_t* n_events,
+                                   const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                   const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                   uint64_t* outbound_next_task, uint64_t* min_deliver);
+
+/* ---------------------------------------------------------------------------------------
+ * A window's results in host buffers, one call each: asynchronous copies of the arrays the stages
+ * own on the context's stream and ONE wait (shd_copy_to_host waits per array).  Host buffers,
+ * pinned for the link's full rate; any pointer may be NULL.
+ *   shd_window_records_host  the last shd_window_open's records: off[n_hosts + 1]; pkt, time, kind
+ *                            of *n_out entries, the buffers holding cap
+ *   shd_window_sent_host     the last close's results: sent_pkt, sent_status of *n_batch entries
+ *                            (cap_batch); loc_off[n_hosts + 1]; loc_pkt, loc_time of *n_local
+ *                            entries (cap_local)
+ * n_hosts: the hosts the window runs here (a sharded rank's own).  SHD_ERR_INVALID: a capacity below
+ * its count while a buffer of that capacity is given -- the counts are returned and nothing is
+ * copied, so the caller sizes its buffers and calls again.  SHD_ERR_STATE: no open (no close) has
+ * succeeded yet, or the arrays are no longer the stage's (set up again, or grown by a later call).
+ * ------------------------------------------------------------------------------------- */
+shd_status shd_window_records_host(shd_ctx* ctx, uint32_t* off, uint32_t* pkt, uint64_t* time, uint8_t* kind,
+                                   uint64_t cap, uint64_t* n_out);
+shd_status shd_window_sent_host(shd_ctx* ctx, uint32_t* sent_pkt, uint8_t* sent_status, uint64_t cap_batch,
+                                uint32_t* loc_off, uint32_t* loc_pkt, uint64_t* loc_time, uint64_t cap_local,
+                                uint64_t* n_batch, uint64_t* n_local);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

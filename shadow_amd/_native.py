@@ -46,6 +46,7 @@ EXPORTED = [
     "shd_equeue_next_batch", "shd_ledger_setup", "shd_ledger_record", "shd_ledger_gather", "shd_ledger_stats",
     "shd_window_open", "shd_window_close", "shd_ledger_record_sharded",
     "shd_outbound_advance_sockets", "shd_window_close_sockets",
+    "shd_offers_group", "shd_window_close_staged", "shd_window_records_host", "shd_window_sent_host",
 ]
 COMM_ID_BYTES = 128
 
@@ -250,6 +251,11 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_window_close": (I32, [P, P, P, P, P, P, P, P, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P, P]),
         "shd_window_close_sockets": (I32, [P, P, P, P, P, P, P, P, P, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P,
                                            P]),
+        "shd_offers_group": (I32, [P, U32, P, P, P, P, P, U32, U64, P, P, P, P, P, P, P, P, P]),
+        "shd_window_close_staged": (I32, [P, U32, P, P, P, P, P, U32, U64, U64, U64, U64, P, P, P, P, P, P, P, P, P, P,
+                                          P]),
+        "shd_window_records_host": (I32, [P, P, P, P, P, U64, P]),
+        "shd_window_sent_host": (I32, [P, P, P, U64, P, P, P, U64, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

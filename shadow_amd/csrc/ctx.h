@@ -170,6 +170,21 @@ struct OutboundState {
     bool ready = false;
 };
 
+// shd_offers_group (offers.hip): the worker threads' staged offers grouped by host into the
+// outbound stage's columns -- the runs as uploaded (or copied out of the pinned stages), each
+// host's run, the records (copy path only), and the grouped columns handed out (engine-owned,
+// valid until the next group).
+struct OffersState {
+    DevBuf runh, runc, runo, rstg;   // per run: host, count, first record in stage order, stage (zero-copy)
+    DevBuf hrun, hcnt;               // per host: its run (+1), its offers
+    DevBuf rec;                      // the records of every stage, stage after stage (copy path)
+    DevBuf tab;                      // zero-copy: the stage table, and its pinned source
+    PinBuf tab_pin;
+    DevBuf red;                      // the two check words
+    DevBuf d_off, d_time, d_prio, d_sock, d_size, d_pay, d_dst, d_pkt;
+    ScanScratch scan;
+};
+
 // The packet ledger (ledger.hip): each batch's (total size, packet id) per packet, kept on the
 // device from the relay round that sent the batch until its last event has popped.
 struct LedgerState {
@@ -200,6 +215,24 @@ struct WindowState {
     // until the next round) and out_batch the number its events were recorded under
     uint64_t out_batch = 0;
     DevBuf no_off;                 // a zero: the batch offsets of a rank without hosts
+    // what shd_window_records_host / shd_window_sent_host fetch: the last open's records and the
+    // last close's results as the stages handed them out (the arrays are the stages' own)
+    struct Records {
+        bool valid = false;
+        const uint32_t *off = nullptr, *pkt = nullptr;
+        const uint64_t* time = nullptr;
+        const uint8_t* kind = nullptr;
+        uint64_t n = 0;
+        uint32_t n_hosts = 0;
+    } rec;
+    struct Sent {
+        bool valid = false;
+        const uint32_t *pkt = nullptr, *loc_off = nullptr, *loc_pkt = nullptr;
+        const uint8_t* status = nullptr;
+        const uint64_t* loc_time = nullptr;
+        uint64_t n_batch = 0, n_local = 0;
+        uint32_t n_hosts = 0;
+    } sent;
 };
 
 struct RelayState {
@@ -298,7 +331,7 @@ struct PreparedGraph {
 
 struct shd_ctx;
 namespace shd {
-// h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [32, 34) flush checks,
+// h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [32, 36) flush checks, [36, 38) offer-group checks,
 // [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker;
 // [81, 86) outbound-stage words
 constexpr int kPinWords = 88;
@@ -377,6 +410,7 @@ struct shd_ctx {
     shd::TbState tb;
     shd::InboundState inb;
     shd::OutboundState outb;
+    shd::OffersState offers;
     shd::LedgerState ledger;
     shd::WindowState win;
 };

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "pin_view.h"
 #include "relay_priv.h"
 #include "scan.h"
 
@@ -194,18 +195,6 @@ __global__ __launch_bounds__(256) void fl_events16(uint64_t n, uint64_t round_en
     if (e >= n) return;
     const uint32_t s = src[e];
     fl_put_event(out, b12 != 0, e, (uint32_t)(deliver[e] - round_end), s, (uint32_t)(seq[e] - seq_base[s]), perm[pkt[e]]);
-}
-
-// a device view of host memory p when it is pinned (hipHostMalloc / registered), else nullptr
-static const void* dev_view(const void* p) {
-    if (!p) return nullptr;
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // pageable memory: not an error of the call
-        return nullptr;
-    }
-    if (at.type != hipMemoryTypeHost || !at.devicePointer || !at.hostPointer) return nullptr;
-    return static_cast<const char*>(at.devicePointer) + (static_cast<const char*>(p) - static_cast<const char*>(at.hostPointer));
 }
 
 }  // namespace shd

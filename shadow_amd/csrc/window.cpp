@@ -6,9 +6,13 @@
 // Under a communicator of more than one rank the window runs on the rank's shard of the hosts: the
 // open is local as before, the close a collective -- the sharded round, then the sharded record,
 // which brings each sent packet's (size, id) to the rank that owns its destination.
+// shd_window_close_staged is the close from the worker threads' staged offers (offers.hip groups
+// them by host first); shd_window_records_host / shd_window_sent_host copy a window's results
+// into host buffers with one wait each.
 // The stages are the ones the separate calls drive (equeue.hip, ledger.hip, inbound.hip,
 // outbound.hip, relay*.hip); this file only chains them and keeps what lies between two calls.
 #include "ctx.h"
+#include "offer_stage.h"
 
 using namespace shd;
 
@@ -61,21 +65,27 @@ static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, cons
                                        const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
                                        uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
                                        const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
-                                       uint64_t* outbound_next_task, uint64_t* min_deliver) {
+                                       uint64_t* outbound_next_task, uint64_t* min_deliver,
+                                       shd_status local = SHD_OK) {
     WindowState& W = ctx->win;
     SHD_HIP(hipSetDevice(ctx->device));
     const uint32_t n_own = window_own_hosts(ctx);
-    // 1. the preconditions, agreed: after this either every rank runs the window or none has
-    shd_status pre = SHD_OK;
+    // 1. the preconditions, agreed: after this either every rank runs the window or none has.
+    //    `local`: what the caller found before the call (the staged close's grouping) -- this
+    //    rank's word in the agreement
+    shd_status pre = local;
     const LedgerBook& B = ctx->ledger.book;
-    if (!window_ready(ctx) || !W.opened) pre = SHD_ERR_STATE;
-    else if (window_end != W.window_end) pre = SHD_ERR_INVALID;
-    else if (n_own && B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) pre = SHD_ERR_INVALID;
-    else if (n_own && n_offers && ctx->outb.with_sockets() && !d_sock) pre = SHD_ERR_INVALID;   // the socket column
-    else if (!n_own) pre = window_no_off(ctx);
+    if (pre == SHD_OK) {
+        if (!window_ready(ctx) || !W.opened) pre = SHD_ERR_STATE;
+        else if (window_end != W.window_end) pre = SHD_ERR_INVALID;
+        else if (n_own && B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) pre = SHD_ERR_INVALID;
+        else if (n_own && n_offers && ctx->outb.with_sockets() && !d_sock) pre = SHD_ERR_INVALID;   // the socket column
+        else if (!n_own) pre = window_no_off(ctx);
+    }
     SHD_TRY(comm_agree(ctx, pre));
     W.opened = false;
     W.has_out = false;
+    W.sent.valid = false;
     // 2. the outbound stage, local; a rank where it fails still enters the round
     shd_batch batch{};
     const uint32_t *b_pkt = nullptr, *b_size = nullptr;
@@ -118,6 +128,92 @@ static shd_status window_close_sharded(shd_ctx* ctx, const uint32_t* d_off, cons
     return SHD_OK;
 }
 
+// an async copy of n elements of a stage's device array into the caller's buffer (either may be absent)
+template <class T>
+static shd_status window_fetch(shd_ctx* ctx, T* dst, const T* d_src, uint64_t n) {
+    if (dst && d_src && n) SHD_HIP(hipMemcpyAsync(dst, d_src, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return SHD_OK;
+}
+
+// the preconditions of a one-context close, before any stage has run
+static shd_status window_close_pre(const shd_ctx* ctx, uint64_t window_end) {
+    const WindowState& W = ctx->win;
+    if (!window_ready(ctx) || !W.opened) return SHD_ERR_STATE;
+    if (window_end != W.window_end) return SHD_ERR_INVALID;
+    // the batch this close may send must find a row: refused here, before any stage has run
+    const LedgerBook& B = ctx->ledger.book;
+    if (B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) return SHD_ERR_INVALID;
+    return SHD_OK;
+}
+
+// The close on the offers as device arrays.  `local` (under a communicator): this rank's status
+// from before the call, its word in the precondition agreement.
+static shd_status window_close_arrays(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
+                                      const uint64_t* d_prio, const uint64_t* d_sock, const uint32_t* d_size,
+                                      const uint32_t* d_payload, const uint32_t* d_dst, const uint32_t* d_pkt,
+                                      uint64_t n_offers, uint64_t window_end, uint64_t sim_end, uint64_t bootstrap_end,
+                                      const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
+                                      uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                      const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                      uint64_t* outbound_next_task, uint64_t* min_deliver, shd_status local) {
+    WindowState& W = ctx->win;
+    // what shd_window_sent_host fetches is kept whichever outputs the caller asked for
+    WindowState::Sent k{};
+    if (!sent_pkt) sent_pkt = &k.pkt;
+    if (!sent_status) sent_status = &k.status;
+    if (!n_batch) n_batch = &k.n_batch;
+    if (!loc_off) loc_off = &k.loc_off;
+    if (!loc_pkt) loc_pkt = &k.loc_pkt;
+    if (!loc_time) loc_time = &k.loc_time;
+    if (!n_local) n_local = &k.n_local;
+    if (window_sharded(ctx)) {
+        // the one refusal without a collective: a relay not set up under this communicator (every
+        // rank sets it up, or none); everything else is agreed between the ranks first
+        if (!ctx->relay.ready || !ctx->relay.sharded) return SHD_ERR_STATE;
+        SHD_TRY(window_close_sharded(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                     window_end, sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off,
+                                     loc_pkt, loc_time, n_local, n_stored, outbound_next_task, min_deliver, local));
+        W.sent = WindowState::Sent{true, *sent_pkt, *loc_off, *loc_pkt, *sent_status, *loc_time, *n_batch, *n_local,
+                                   window_own_hosts(ctx)};
+        return SHD_OK;
+    }
+    SHD_TRY(window_close_pre(ctx, window_end));
+    shd_batch batch{};
+    const uint32_t* b_pkt = nullptr;
+    SHD_TRY(shd_outbound_advance_sockets(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers,
+                                         window_end, bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local,
+                                         n_stored, outbound_next_task));
+    W.opened = false;
+    W.has_out = false;
+    W.sent.valid = false;
+    uint64_t sent = 0, low = ~0ull;
+    if (batch.n_packets) {
+        shd_relay_out out{};
+        SHD_TRY(shd_equeue_batch_buffers(ctx, batch.n_packets, &out));
+        SHD_TRY(W.status.ensure(batch.n_packets));
+        out.status = W.status.as<uint8_t>();
+        const shd_round round{window_end, sim_end, bootstrap_end};
+        SHD_TRY(shd_relay_round_device(ctx, &batch, &round, &out));
+        uint64_t number = 0;
+        const uint32_t* b_size = nullptr;
+        SHD_TRY(shd_equeue_next_batch(ctx, &number));
+        SHD_TRY(shd_outbound_sent_sizes(ctx, &b_size));
+        SHD_TRY(shd_ledger_record(ctx, number, b_size, b_pkt, batch.n_packets, out.n_sent));
+        W.out = out;
+        W.has_out = true;
+        sent = out.n_sent;
+        low = out.min_deliver;
+    }
+    *sent_pkt = b_pkt;
+    *sent_status = W.status.as<uint8_t>();
+    *n_batch = batch.n_packets;
+    if (n_events) *n_events = sent;
+    if (min_deliver) *min_deliver = low;
+    W.sent = WindowState::Sent{true, b_pkt, *loc_off, *loc_pkt, *sent_status, *loc_time, batch.n_packets, *n_local,
+                               ctx->outb.n_hosts};
+    return SHD_OK;
+}
+
 extern "C" {
 
 shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap_end, const uint32_t** out_off,
@@ -127,10 +223,12 @@ shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap
     if (!ctx) return SHD_ERR_INVALID;
     WindowState& W = ctx->win;
     if (!window_ready(ctx) || W.opened) return SHD_ERR_STATE;
+    W.rec.valid = false;
     if (window_sharded(ctx)) {
         if (window_own_hosts(ctx) == 0) {   // a rank without hosts: nothing pops, nothing is delivered
             SHD_HIP(hipSetDevice(ctx->device));
             SHD_TRY(window_no_off(ctx));
+            W.rec = WindowState::Records{true, W.no_off.as<uint32_t>(), nullptr, nullptr, nullptr, 0, 0};
             if (out_off) *out_off = W.no_off.as<uint32_t>();
             if (out_pkt) *out_pkt = nullptr;
             if (out_time) *out_time = nullptr;
@@ -156,8 +254,17 @@ shd_status shd_window_open(shd_ctx* ctx, uint64_t window_end, uint64_t bootstrap
     W.has_out = false;
     const uint32_t *d_size = nullptr, *d_pkt = nullptr;
     SHD_TRY(shd_ledger_gather(ctx, eo.tag, eo.n_popped, &d_size, &d_pkt));
-    SHD_TRY(shd_inbound_advance(ctx, eo.off, eo.deliver, d_size, d_pkt, eo.n_popped, window_end, bootstrap_end, out_off,
-                                out_pkt, out_time, out_kind, n_out, n_stored, inbound_next_task));
+    WindowState::Records r{};
+    SHD_TRY(shd_inbound_advance(ctx, eo.off, eo.deliver, d_size, d_pkt, eo.n_popped, window_end, bootstrap_end, &r.off,
+                                &r.pkt, &r.time, &r.kind, &r.n, n_stored, inbound_next_task));
+    r.n_hosts = ctx->inb.n_hosts;
+    r.valid = true;
+    W.rec = r;
+    if (out_off) *out_off = r.off;
+    if (out_pkt) *out_pkt = r.pkt;
+    if (out_time) *out_time = r.time;
+    if (out_kind) *out_kind = r.kind;
+    if (n_out) *n_out = r.n;
     if (n_popped) *n_popped = eo.n_popped;
     if (n_pending) *n_pending = eo.n_pending;
     if (queue_next_time) *queue_next_time = eo.next_time;
@@ -175,51 +282,96 @@ shd_status shd_window_close_sockets(shd_ctx* ctx, const uint32_t* d_off, const u
                                     const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
                                     uint64_t* outbound_next_task, uint64_t* min_deliver) {
     if (!ctx) return SHD_ERR_INVALID;
-    WindowState& W = ctx->win;
+    return window_close_arrays(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
+                               sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off, loc_pkt, loc_time,
+                               n_local, n_stored, outbound_next_task, min_deliver, SHD_OK);
+}
+
+shd_status shd_window_close_staged(shd_ctx* ctx, uint32_t n_stages, const uint32_t* stage_runs,
+                                   const uint32_t** run_host, const uint32_t** run_count, const uint64_t* stage_offers,
+                                   const uint32_t** offers, uint32_t offer_words, uint64_t time_base,
+                                   uint64_t window_end, uint64_t sim_end, uint64_t bootstrap_end,
+                                   const uint32_t** sent_pkt, const uint8_t** sent_status, uint64_t* n_batch,
+                                   uint64_t* n_events, const uint32_t** loc_off, const uint32_t** loc_pkt,
+                                   const uint64_t** loc_time, uint64_t* n_local, uint64_t* n_stored,
+                                   uint64_t* outbound_next_task, uint64_t* min_deliver) {
+    if (!ctx) return SHD_ERR_INVALID;
+    const uint32_t *d_off = nullptr, *d_size = nullptr, *d_payload = nullptr, *d_dst = nullptr, *d_pkt = nullptr;
+    const uint64_t *d_time = nullptr, *d_prio = nullptr, *d_sock = nullptr;
+    uint64_t n_offers = 0;
+    shd_status local = SHD_OK;
     if (window_sharded(ctx)) {
-        // the one refusal without a collective: a relay not set up under this communicator (every
-        // rank sets it up, or none); everything else is agreed between the ranks first
         if (!ctx->relay.ready || !ctx->relay.sharded) return SHD_ERR_STATE;
-        return window_close_sharded(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
-                                    sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off, loc_pkt,
-                                    loc_time, n_local, n_stored, outbound_next_task, min_deliver);
+        // the grouping first and locally, no collective: its status is this rank's word in the
+        // agreement, so a refusal here is every rank's and no rank has run a stage
+        if (window_own_hosts(ctx) == 0) {
+            // a rank without hosts stages nothing (n_stages = 0): any run names a host it does not have
+            uint64_t n_runs = 0;
+            if (!offer_stages_ok(n_stages, stage_runs, run_host, run_count, stage_offers, offers, offer_words, false,
+                                 &n_runs, nullptr))
+                local = SHD_ERR_INVALID;
+            else if (n_runs)
+                local = SHD_ERR_NO_HOST;
+        } else {
+            local = shd_offers_group(ctx, n_stages, stage_runs, run_host, run_count, stage_offers, offers, offer_words,
+                                     time_base, &d_off, &d_time, &d_prio, &d_sock, &d_size, &d_payload, &d_dst, &d_pkt,
+                                     &n_offers);
+        }
+    } else {
+        // the window's own preconditions first; a failed grouping leaves the window open and no
+        // stage run, so a corrected close may follow
+        SHD_TRY(window_close_pre(ctx, window_end));
+        SHD_TRY(shd_offers_group(ctx, n_stages, stage_runs, run_host, run_count, stage_offers, offers, offer_words,
+                                 time_base, &d_off, &d_time, &d_prio, &d_sock, &d_size, &d_payload, &d_dst, &d_pkt,
+                                 &n_offers));
     }
-    if (!window_ready(ctx) || !W.opened) return SHD_ERR_STATE;
-    if (window_end != W.window_end) return SHD_ERR_INVALID;
-    // the batch this close may send must find a row: refused here, before any stage has run
-    const LedgerBook& B = ctx->ledger.book;
-    if (B.oldest != kLedgerNone && ctx->eq.batches - B.oldest >= B.max_live) return SHD_ERR_INVALID;
-    shd_batch batch{};
-    const uint32_t* b_pkt = nullptr;
-    SHD_TRY(shd_outbound_advance_sockets(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers,
-                                         window_end, bootstrap_end, &batch, &b_pkt, loc_off, loc_pkt, loc_time, n_local,
-                                         n_stored, outbound_next_task));
-    W.opened = false;
-    W.has_out = false;
-    uint64_t sent = 0, low = ~0ull;
-    if (batch.n_packets) {
-        shd_relay_out out{};
-        SHD_TRY(shd_equeue_batch_buffers(ctx, batch.n_packets, &out));
-        SHD_TRY(W.status.ensure(batch.n_packets));
-        out.status = W.status.as<uint8_t>();
-        const shd_round round{window_end, sim_end, bootstrap_end};
-        SHD_TRY(shd_relay_round_device(ctx, &batch, &round, &out));
-        uint64_t number = 0;
-        const uint32_t* b_size = nullptr;
-        SHD_TRY(shd_equeue_next_batch(ctx, &number));
-        SHD_TRY(shd_outbound_sent_sizes(ctx, &b_size));
-        SHD_TRY(shd_ledger_record(ctx, number, b_size, b_pkt, batch.n_packets, out.n_sent));
-        W.out = out;
-        W.has_out = true;
-        sent = out.n_sent;
-        low = out.min_deliver;
-    }
-    if (sent_pkt) *sent_pkt = b_pkt;
-    if (sent_status) *sent_status = W.status.as<uint8_t>();
-    if (n_batch) *n_batch = batch.n_packets;
-    if (n_events) *n_events = sent;
-    if (min_deliver) *min_deliver = low;
-    return SHD_OK;
+    return window_close_arrays(ctx, d_off, d_time, d_prio, d_sock, d_size, d_payload, d_dst, d_pkt, n_offers, window_end,
+                               sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off, loc_pkt, loc_time,
+                               n_local, n_stored, outbound_next_task, min_deliver, local);
+}
+
+shd_status shd_window_records_host(shd_ctx* ctx, uint32_t* off, uint32_t* pkt, uint64_t* time, uint8_t* kind,
+                                   uint64_t cap, uint64_t* n_out) {
+    if (!ctx) return SHD_ERR_INVALID;
+    const WindowState::Records& R = ctx->win.rec;
+    const InboundState& I = ctx->inb;
+    // the arrays are the inbound stage's: gone when it was set up again or its buffers grew since
+    if (!R.valid) return SHD_ERR_STATE;
+    if (R.n_hosts && (!I.ready || I.n_hosts != R.n_hosts || R.off != I.o_off.p || R.pkt != I.o_pkt.p ||
+                      R.time != I.o_time.p || R.kind != I.o_kind.p))
+        return SHD_ERR_STATE;
+    if (n_out) *n_out = R.n;
+    if ((pkt || time || kind) && cap < R.n) return SHD_ERR_INVALID;
+    SHD_HIP(hipSetDevice(ctx->device));
+    SHD_TRY(window_fetch(ctx, off, R.off, (uint64_t)R.n_hosts + 1));
+    SHD_TRY(window_fetch(ctx, pkt, R.pkt, R.n));
+    SHD_TRY(window_fetch(ctx, time, R.time, R.n));
+    SHD_TRY(window_fetch(ctx, kind, R.kind, R.n));
+    return wait_stream(ctx, ctx->stream);
+}
+
+shd_status shd_window_sent_host(shd_ctx* ctx, uint32_t* sent_pkt, uint8_t* sent_status, uint64_t cap_batch,
+                                uint32_t* loc_off, uint32_t* loc_pkt, uint64_t* loc_time, uint64_t cap_local,
+                                uint64_t* n_batch, uint64_t* n_local) {
+    if (!ctx) return SHD_ERR_INVALID;
+    const WindowState::Sent& S = ctx->win.sent;
+    const OutboundState& O = ctx->outb;
+    // the arrays are the outbound stage's and the window's status array
+    if (!S.valid) return SHD_ERR_STATE;
+    if (S.n_hosts && (!O.ready || O.n_hosts != S.n_hosts || S.pkt != O.b_pkt.p || S.loc_off != O.loc_off.p ||
+                      S.loc_pkt != O.l_pkt.p || S.loc_time != O.l_time.p || S.status != ctx->win.status.p))
+        return SHD_ERR_STATE;
+    if (n_batch) *n_batch = S.n_batch;
+    if (n_local) *n_local = S.n_local;
+    if (((sent_pkt || sent_status) && cap_batch < S.n_batch) || ((loc_pkt || loc_time) && cap_local < S.n_local))
+        return SHD_ERR_INVALID;
+    SHD_HIP(hipSetDevice(ctx->device));
+    SHD_TRY(window_fetch(ctx, sent_pkt, S.pkt, S.n_batch));
+    SHD_TRY(window_fetch(ctx, sent_status, S.status, S.n_batch));
+    SHD_TRY(window_fetch(ctx, loc_off, S.loc_off, (uint64_t)S.n_hosts + 1));
+    SHD_TRY(window_fetch(ctx, loc_pkt, S.loc_pkt, S.n_local));
+    SHD_TRY(window_fetch(ctx, loc_time, S.loc_time, S.n_local));
+    return wait_stream(ctx, ctx->stream);
 }
 
 shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time, const uint64_t* d_prio,

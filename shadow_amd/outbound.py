@@ -21,7 +21,10 @@ qdisc="fifo", max_sockets=64)`` -- bucket parameters per host, all three 0 for a
 ``first_host + h`` -- or ``OutboundStage.from_bandwidth(engine, bytes_per_second, start)``.
 ``advance(off, time, prio, size, payload, dst, pkt, window_end=...)`` consumes one window's offers
 grouped by host (host arrays; ``advance_device`` takes them as they lie on the GPU) and returns the
-packets sent, as the batch a relay round takes, and the local deliveries.  No CPU fallback: without
+packets sent, as the batch a relay round takes, and the local deliveries.  ``OfferStages`` holds
+the same offers as the worker threads stage them -- per thread the runs ``(host, count)`` and 8-
+or 10-word records -- and ``group_stages`` (``shd_offers_group``) groups them by host on the
+device into the arrays ``advance_device`` takes.  No CPU fallback: without
 the native library or a gfx950 GPU every call raises.
 """
 from __future__ import annotations
@@ -80,6 +83,160 @@ class Sent:
         return list(zip(self.loc_pkt[a:b].tolist(), self.loc_time[a:b].tolist()))
 
 
+OFFER_WORDS, OFFER_WORDS_SOCK = 8, 10   # u32 words per staged offer (csrc/offer_stage.h)
+
+
+def group_offers(run_host, run_count, offers, words: int, time_base: int, n_hosts: int, first_host: int = 0):
+    """The numpy statement of ``shd_offers_group``: per-thread stages (lists of ``run_host``,
+    ``run_count`` and ``[n, words]`` u32 record arrays) -> ``(off, time, prio, sock, size, payload,
+    dst, pkt)`` grouped by host in host order, each host's offers in the order its run holds them
+    (``sock`` is None at width 8).  Raises ValueError where the engine refuses."""
+    if words not in (OFFER_WORDS, OFFER_WORDS_SOCK):
+        raise ValueError("offer_words")
+    host = np.concatenate([np.asarray(h, np.uint32) for h in run_host] + [np.zeros(0, np.uint32)]).astype(np.int64)
+    count = np.concatenate([np.asarray(c, np.uint32) for c in run_count] + [np.zeros(0, np.uint32)]).astype(np.int64)
+    for c, o in zip(run_count, offers):
+        if int(np.asarray(c, np.int64).sum()) != len(np.asarray(o).reshape(-1, words)):
+            raise ValueError("a stage's run counts do not add up to its offers")
+    rec = np.concatenate([np.asarray(o, np.uint32).reshape(-1, words) for o in offers] +
+                         [np.zeros((0, words), np.uint32)])
+    local = host - first_host
+    if ((local < 0) | (local >= n_hosts)).any():
+        raise ValueError("a run of a host outside the stage")
+    if len(np.unique(local)) != len(local):
+        raise ValueError("a host with two runs")
+    owner = np.repeat(local, count)                   # each record's host, in stage order
+    order = np.argsort(owner, kind="stable")          # the group-by: stable, so a run keeps its order
+    rec = rec[order]
+    off = np.zeros(n_hosts + 1, np.uint32)
+    off[1:] = np.cumsum(np.bincount(owner, minlength=n_hosts))
+    u64 = lambda lo: rec[:, lo].astype(np.uint64) | (rec[:, lo + 1].astype(np.uint64) << np.uint64(32))  # noqa: E731
+    return (off, np.uint64(time_base) + rec[:, 0].astype(np.uint64), u64(6), u64(8) if words == OFFER_WORDS_SOCK else None,
+            rec[:, 2].copy(), rec[:, 3].copy(), rec[:, 1].copy(), rec[:, 4].copy())
+
+
+class OfferStages:
+    """One window's offers as the worker threads stage them for ``shd_offers_group`` /
+    ``shd_window_close_staged``: per thread the runs ``(host, count)`` and the ``words``-word
+    records, run after run.  ``from_grouped`` deals the hosts of grouped offers to threads, as a
+    thread-per-core scheduler does; ``pinned`` moves every array into ``shd_host_alloc`` memory, where
+    the engine reads it in place."""
+
+    def __init__(self, run_host, run_count, offers, words: int):
+        self.words = int(words)
+        self.run_host = [np.ascontiguousarray(h, np.uint32) for h in run_host]
+        self.run_count = [np.ascontiguousarray(c, np.uint32) for c in run_count]
+        self.offers = [np.ascontiguousarray(o, np.uint32).reshape(-1, self.words) for o in offers]
+        self.lib, self.allocs = None, []
+        self._point([(h.ctypes.data, c.ctypes.data, o.ctypes.data)
+                     for h, c, o in zip(self.run_host, self.run_count, self.offers)])
+
+    def _point(self, ptrs):
+        n = len(self.run_host)
+        self.n_stages = n
+        self.n_offers = sum(len(o) for o in self.offers)
+        self.stage_runs = (C.c_uint32 * max(n, 1))(*[len(h) for h in self.run_host])
+        self.stage_offers = (C.c_uint64 * max(n, 1))(*[len(o) for o in self.offers])
+        self.p_host, self.p_count, self.p_offers = ((C.c_void_p * max(n, 1))(*[p[i] for p in ptrs]) for i in range(3))
+
+    @classmethod
+    def from_grouped(cls, off, time, prio, size, payload, dst, pkt, *, time_base: int, n_threads: int,
+                     first_host: int = 0, sock=None, words: int | None = None, seed: int = 7, idle=(),
+                     keep_empty: float = 0.5):
+        """Offers grouped by host (``OutboundStage.advance``'s arrays) -> stages.  Every host goes
+        to one of the ``n_threads`` threads not listed in ``idle`` and each thread runs its hosts
+        in a shuffled order; a host without offers keeps a run of count 0 with probability
+        ``keep_empty``.  ``words``: 10 when ``sock`` is given, else 8."""
+        words = words or (OFFER_WORDS_SOCK if sock is not None else OFFER_WORDS)
+        rng = np.random.default_rng(seed)
+        off = np.asarray(off, np.int64)
+        H, n = len(off) - 1, int(off[-1])
+        rec = np.zeros((n, words), np.uint32)
+        t = np.asarray(time, np.uint64) - np.uint64(time_base)
+        assert n == 0 or int(t.max()) < 2**32, "time_off is 32 bits"
+        lo32, hi32 = (lambda a: (np.asarray(a, np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32),
+                      lambda a: (np.asarray(a, np.uint64) >> np.uint64(32)).astype(np.uint32))
+        rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4] = t.astype(np.uint32), dst, size, payload, pkt
+        rec[:, 6], rec[:, 7] = lo32(prio), hi32(prio)
+        if words == OFFER_WORDS_SOCK and sock is not None:
+            rec[:, 8], rec[:, 9] = lo32(sock), hi32(sock)
+        busy = np.array([k for k in range(n_threads) if k not in set(idle)], np.int64)
+        cnt = np.diff(off)
+        thread = busy[rng.integers(0, len(busy), H)] if H else np.zeros(0, np.int64)
+        staged = (cnt > 0) | (rng.random(H) < keep_empty)
+        run_host, run_count, offers = [], [], []
+        for k in range(n_threads):
+            hs = np.flatnonzero((thread == k) & staged)
+            rng.shuffle(hs)
+            c = cnt[hs]
+            idx = np.repeat(off[hs] - (np.cumsum(c) - c), c) + np.arange(int(c.sum()))
+            run_host.append((hs + first_host).astype(np.uint32))
+            run_count.append(c.astype(np.uint32))
+            offers.append(rec[idx])
+        return cls(run_host, run_count, offers, words)
+
+    def grouped(self, time_base: int, n_hosts: int, first_host: int = 0):
+        """``group_offers`` of these stages."""
+        return group_offers(self.run_host, self.run_count, self.offers, self.words, time_base, n_hosts, first_host)
+
+    def pinned(self, lib, which=None) -> "OfferStages":
+        """A copy whose arrays lie in ``shd_host_alloc`` memory (``which``: only the stages it
+        lists; the others stay pageable); ``free`` returns the memory."""
+        p = OfferStages(self.run_host, self.run_count, self.offers, self.words)
+        p.lib = lib
+        ptrs = []
+        for k, arrs in enumerate(zip(p.run_host, p.run_count, p.offers)):
+            row = []
+            for a in arrs:
+                if which is not None and k not in which:
+                    row.append(a.ctypes.data)
+                    continue
+                ptr = lib.shd_host_alloc(max(a.nbytes, 1))
+                if not ptr:
+                    p.free()
+                    raise MemoryError("shd_host_alloc")
+                p.allocs.append(ptr)
+                C.memmove(ptr, a.ctypes.data, a.nbytes)
+                row.append(ptr)
+            ptrs.append(tuple(row))
+        p._point(ptrs)
+        return p
+
+    def free(self):
+        for ptr in self.allocs:
+            self.lib.shd_host_free(ptr)
+        self.allocs = []
+
+    def args(self):
+        """The stage arguments of ``shd_offers_group`` / ``shd_window_close_staged``."""
+        return (self.n_stages, self.stage_runs, self.p_host, self.p_count, self.stage_offers, self.p_offers, self.words)
+
+
+@dataclass
+class GroupedOffers:
+    """``shd_offers_group``'s outputs: engine-owned device pointers (valid until the next group),
+    in the order ``OutboundStage.advance_device`` takes them (``d_sock`` by keyword)."""
+    d_off: int
+    d_time: int
+    d_prio: int
+    d_size: int
+    d_payload: int
+    d_dst: int
+    d_pkt: int
+    n_offers: int
+    d_sock: int | None
+
+
+def group_stages(engine, stages: OfferStages, time_base: int) -> GroupedOffers:
+    """``shd_offers_group`` on the engine's outbound stage (``OutboundStage.group_stages``)."""
+    o = [C.c_void_p() for _ in range(8)]
+    n = C.c_uint64(0)
+    N.check(engine.lib.shd_offers_group(engine.ctx, *stages.args(), int(time_base), *map(C.byref, o), C.byref(n)),
+            "shd_offers_group")
+    d_off, d_time, d_prio, d_sock, d_size, d_pay, d_dst, d_pkt = (x.value for x in o)
+    return GroupedOffers(d_off, d_time, d_prio, d_size, d_pay, d_dst, d_pkt, n.value, d_sock)
+
+
 class OutboundStage:
     def __init__(self, engine, capacity, refill_increment, refill_interval, last_refill=SIM_START,
                  first_host: int = 0, ring_capacity: int = 4096, qdisc: str = "fifo", max_sockets: int = 64):
@@ -128,6 +285,25 @@ class OutboundStage:
             "shd_outbound_advance")
         return DeviceBatch(b, sp.value, lo.value, lp.value, lt.value, b.n_packets, n_local.value, n_stored.value,
                            nxt.value)
+
+    def group_stages(self, stages: OfferStages, time_base: int) -> GroupedOffers:
+        """``shd_offers_group``: the threads' staged offers grouped by host on the device, into
+        the arrays ``advance_device`` takes: ``g = stage.group_stages(st, base)``, then
+        ``stage.advance_device(g.d_off, g.d_time, g.d_prio, g.d_size, g.d_payload, g.d_dst, g.d_pkt,
+        g.n_offers, window_end, d_sock=g.d_sock)``."""
+        return group_stages(self.eng, stages, time_base)
+
+    def grouped_host(self, g: GroupedOffers):
+        """Host copies of a group's arrays: ``(off, time, prio, sock, size, payload, dst, pkt)``,
+        ``sock`` None at width 8."""
+        n = g.n_offers
+        out = [np.zeros(self.n_hosts + 1, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64),
+               np.zeros(n, np.uint64) if g.d_sock else None] + [np.zeros(n, np.uint32) for _ in range(4)]
+        for dst, src in zip(out, (g.d_off, g.d_time, g.d_prio, g.d_sock, g.d_size, g.d_payload, g.d_dst, g.d_pkt)):
+            if dst is not None and dst.nbytes:
+                N.check(self.eng.lib.shd_copy_to_host(self.eng.ctx, N.ptr(dst), C.c_void_p(src), dst.nbytes),
+                        "shd_copy_to_host")
+        return tuple(out)
 
     def advance(self, off=None, time=None, prio=None, size=None, payload=None, dst=None, pkt=None, *,
                 window_end: int, bootstrap_end: int = 0, sock=None) -> Sent:

@@ -4,7 +4,9 @@ A window is two engine calls with the CPU in between: ``open`` merges the relay 
 close left into the event queues, pops the window's events, gathers their sizes and ids from the
 packet ledger and runs the inbound stage; the caller's sockets turn the inbound records into this
 window's offers; ``close`` runs the outbound stage, the relay round and the ledger record.  No
-packet data crosses the host.  The relay, the event queues, the runahead, both stages and the
+packet data crosses the host.  ``close_staged`` is the close from the worker threads' staged offers
+(``shadow_amd.outbound.OfferStages``), grouped by host on the device; ``records_host`` /
+``closed_host`` fetch a window's results with one engine call each.  The relay, the event queues, the runahead, both stages and the
 ledger are set up by the caller (``Relay``, ``EventQueues``, ``Runahead``, ``InboundStage``,
 ``OutboundStage``, ``PacketLedger``) on one engine, for the same hosts.
 
@@ -100,6 +102,44 @@ class Window:
             C.byref(n_stored), C.byref(nxt), C.byref(md)), "shd_window_close")
         return Closed(sp.value, ss.value, lo.value, lp.value, lt.value, n_batch.value, n_ev.value, n_local.value,
                       n_stored.value, nxt.value, md.value)
+
+    def close_staged(self, stages, time_base: int, window_end: int, sim_end: int, bootstrap_end: int = 0) -> Closed:
+        """``shd_window_close_staged``: the close from the worker threads' staged offers
+        (``shadow_amd.outbound.OfferStages``), grouped by host on the device.  A refused staging
+        (ShdError) leaves the window open: a corrected close may follow.  A rank without hosts
+        passes stages without a thread (``OfferStages([], [], [], 8)``)."""
+        sp, ss, lo, lp, lt = (C.c_void_p() for _ in range(5))
+        n_batch, n_ev, n_local, n_stored, nxt, md = (C.c_uint64(0) for _ in range(6))
+        N.check(self.eng.lib.shd_window_close_staged(
+            self.eng.ctx, *stages.args(), int(time_base), int(window_end), int(sim_end), int(bootstrap_end),
+            C.byref(sp), C.byref(ss), C.byref(n_batch), C.byref(n_ev), C.byref(lo), C.byref(lp), C.byref(lt),
+            C.byref(n_local), C.byref(n_stored), C.byref(nxt), C.byref(md)), "shd_window_close_staged")
+        return Closed(sp.value, ss.value, lo.value, lp.value, lt.value, n_batch.value, n_ev.value, n_local.value,
+                      n_stored.value, nxt.value, md.value)
+
+    def records_host(self, o: Opened) -> Records:
+        """``records`` in one engine call (``shd_window_records_host``): every array copied
+        asynchronously, one wait.  ``o`` must be the last open."""
+        r = o.records
+        off = np.zeros(self.n_hosts + 1, np.uint32)
+        pkt, time, kind = np.zeros(r.n_out, np.uint32), np.zeros(r.n_out, np.uint64), np.zeros(r.n_out, np.uint8)
+        n = C.c_uint64(0)
+        N.check(self.eng.lib.shd_window_records_host(self.eng.ctx, N.ptr(off), N.ptr(pkt), N.ptr(time), N.ptr(kind),
+                                                     r.n_out, C.byref(n)), "shd_window_records_host")
+        assert n.value == r.n_out, "not the last open"
+        return Records(off, pkt, time, kind, r.n_stored, r.next_task_time)
+
+    def closed_host(self, c: Closed) -> ClosedHost:
+        """``closed`` in one engine call (``shd_window_sent_host``).  ``c`` must be the last close."""
+        sp, ss = np.zeros(c.n_batch, np.uint32), np.zeros(c.n_batch, np.uint8)
+        lo = np.zeros(self.n_hosts + 1, np.uint32)
+        lp, lt = np.zeros(c.n_local, np.uint32), np.zeros(c.n_local, np.uint64)
+        nb, nl = C.c_uint64(0), C.c_uint64(0)
+        N.check(self.eng.lib.shd_window_sent_host(self.eng.ctx, N.ptr(sp), N.ptr(ss), c.n_batch, N.ptr(lo), N.ptr(lp),
+                                                  N.ptr(lt), c.n_local, C.byref(nb), C.byref(nl)),
+                "shd_window_sent_host")
+        assert (nb.value, nl.value) == (c.n_batch, c.n_local), "not the last close"
+        return ClosedHost(sp, ss, lo, lp, lt)
 
     def _copy(self, pairs):
         for dst, src in pairs:

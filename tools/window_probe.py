@@ -28,7 +28,18 @@ shd_ledger_record_sharded -- with the ranks entering each timed call together.  
 median over the timed windows of the slowest rank's host clock.  The kernels of the sharded record
 (ledger_pack_count, ledger_pack_scatter, the scan, ledger_remap, ledger_record_ent) are read from
 a kernel trace of this run; the rest of the call is its sizing all-to-all with its read-back and
-the exchange.  --remap-search: the record's remap by binary search instead of its inverse table."""
+the exchange.  --remap-search: the record's remap by binary search instead of its inverse table.
+
+    python tools/window_probe.py --staged THREADS [the same options]
+
+The front door of the close, three ways on the same workload (same seeds, fresh stages each):
+  (a) device   shd_window_close on offers that already lie grouped on the device (the yardstick)
+  (b) staged   shd_window_close_staged from THREADS pinned per-thread stages (hosts dealt to
+               threads, shuffled; 32-byte records)
+  (c) host     what a caller did before: the same stages grouped by host on the CPU (numpy's stable
+               sort), the seven arrays copied from pinned memory, then shd_window_close -- the
+               three parts timed apart
+Medians over the last --timed windows; the opens of every mode are printed too."""
 from __future__ import annotations
 
 import argparse
@@ -57,9 +68,13 @@ def main():
     ap.add_argument("--ring", type=int, default=1024)
     ap.add_argument("--ranks", type=int, default=1)
     ap.add_argument("--remap-search", action="store_true", help="--ranks: knob LEDGER_REMAP_SEARCH=1")
+    ap.add_argument("--staged", type=int, default=0, metavar="THREADS",
+                    help="the close three ways: device arrays, THREADS pinned stages, host group-by + copies")
     a = ap.parse_args()
     if a.ranks > 1:
         return sharded(a)
+    if a.staged:
+        return staged(a)
 
     import numpy as np
     import torch
@@ -189,6 +204,132 @@ def main():
     res["open_ms_all"] = [round(x, 3) for x in t_open]
     res["close_ms_all"] = [round(x, 3) for x in t_close]
     res["gather_ms_all"] = [round(x, 3) for x in t["gather"]]
+    print(json.dumps(res))
+
+
+def staged(a):
+    import numpy as np
+    import torch
+    from shadow_amd import synth
+    from shadow_amd.equeue import EventQueues
+    from shadow_amd.inbound import InboundStage
+    from shadow_amd.ledger import PacketLedger
+    from shadow_amd.outbound import OfferStages, OutboundStage, group_offers
+    from shadow_amd.relay import Relay
+    from shadow_amd.rounds import Runahead
+    from shadow_amd.routing import Engine
+    from shadow_amd.tbucket import SIM_START
+    from shadow_amd.window import Window
+
+    H, NN = a.hosts, a.nodes
+    rs = np.random.default_rng(11)
+    lat = rs.integers(MS, a.lat_windows * MS + 1, (NN, NN)).astype(np.uint64)
+    lat[0, 0] = MS
+    loss = np.full((NN, NN), 0.01, np.float32)
+    host_node = synth.c5_host_nodes(H, NN)
+    rng0 = synth.host_rng_states(H, 1)
+    end_time = SIM_START + 10**12
+
+    def window(g, start, w):   # main()'s workload
+        lo, hi = max(a.per_host * 4 // 5, 0), a.per_host * 6 // 5 + 1
+        cnt = torch.randint(lo, hi, (H,), generator=g, device="cuda")
+        off = torch.zeros(H + 1, dtype=torch.int64, device="cuda")
+        off[1:] = torch.cumsum(cnt, 0)
+        n = int(off[-1])
+        host = torch.repeat_interleave(torch.arange(H, device="cuda"), cnt)
+        key, _ = torch.sort(host * MS + torch.randint(0, MS, (n,), generator=g, device="cuda"))
+        t = start + (key - host * MS)
+        u = torch.rand(n, generator=g, device="cuda")
+        size = torch.where(u < 0.2, 52, torch.where(u < 0.8, 1500, torch.randint(HEADER, 1501, (n,), generator=g,
+                                                                                   device="cuda")))
+        idx = torch.arange(n, device="cuda")
+        dst = torch.randint(0, H, (n,), generator=g, device="cuda")
+        pkt = ((idx + w * 50_000_000) & 0x7FFFFFFF).int()
+        return (off.int(), t.contiguous(), (idx + (w << 32)).contiguous(), size.int(), (size - HEADER).int(), dst.int(),
+                pkt), n
+
+    def setup(eng):
+        return [Relay(host_node, rng0, np.zeros(H, np.uint64), lat, loss, engine=eng), EventQueues(eng, H),
+                Runahead(eng, False, MS),
+                OutboundStage.from_bandwidth(eng, [125_000_000] * H, SIM_START, ring_capacity=a.ring),
+                InboundStage.from_bandwidth(eng, [125_000_000] * H, SIM_START, ring_capacity=a.ring),
+                PacketLedger(eng)]
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    def stages_of(arr, start, w):
+        """The window's offers as the worker threads would have staged them (host memory)."""
+        cols = [x.cpu().numpy() for x in arr]
+        cols = [c.view(np.dtype(f"u{c.dtype.itemsize}")) for c in cols]
+        return OfferStages.from_grouped(*cols, time_base=start, n_threads=a.staged, seed=w, keep_empty=1.0)
+
+    k = a.timed
+    med = lambda x: round(statistics.median(x[-k:]), 3)  # noqa: E731
+    res = {"hosts": H, "nodes": NN, "lat_windows": a.lat_windows, "threads": a.staged}
+    shapes = {}
+    for mode in ("device", "staged", "host"):
+        with Engine(0) as eng:
+            parts = setup(eng)
+            win = Window(eng, H)
+            g = torch.Generator(device="cuda").manual_seed(5)
+            t = {x: [] for x in ("open", "close", "groupby", "h2d", "bytes")}
+            start, shape, pin, dev = SIM_START, [], None, None
+            for w in range(a.windows):
+                arr, n = window(g, start, w)
+                st = stages_of(arr, start, w) if mode != "device" else None
+                op, ms = clock(lambda: win.open(start + MS))
+                t["open"].append(ms)
+                if mode == "device":
+                    cl, ms = clock(lambda: win.close(*arr, n, start + MS, end_time))
+                elif mode == "staged":
+                    held = st.pinned(eng.lib)
+                    try:
+                        cl, ms = clock(lambda: win.close_staged(held, start, start + MS, end_time))
+                    finally:
+                        held.free()
+                    t["bytes"].append(n * 4 * st.words + 8 * sum(len(h) for h in st.run_host))
+                else:
+                    if pin is None:   # the caller's seven pinned arrays and their device copies, allocated once
+                        room = H * (a.per_host * 6 // 5 + 1)
+                        kinds = (torch.int32, torch.int64, torch.int64, torch.int32, torch.int32, torch.int32, torch.int32)
+                        pin = [torch.empty(H + 1 if i == 0 else room, dtype=d, pin_memory=True) for i, d in enumerate(kinds)]
+                        dev = [torch.empty(p.shape, dtype=p.dtype, device="cuda") for p in pin]
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    c = group_offers(st.run_host, st.run_count, st.offers, st.words, start, H)
+                    cols = (c[0], c[1], c[2], c[4], c[5], c[6], c[7])
+                    t1 = time.perf_counter()
+                    for p, d, col in zip(pin, dev, cols):
+                        p.numpy()[:len(col)] = col.view(np.dtype(f"i{col.dtype.itemsize}"))
+                        d[:len(col)].copy_(p[:len(col)], non_blocking=True)
+                    torch.cuda.synchronize()
+                    t2 = time.perf_counter()
+                    cl = win.close(*dev, n, start + MS, end_time)
+                    ms = (time.perf_counter() - t2) * 1e3
+                    t["groupby"].append((t1 - t0) * 1e3)
+                    t["h2d"].append((t2 - t1) * 1e3)
+                t["close"].append(ms)
+                shape.append((n, op.n_popped, op.n_pending, cl.n_batch, cl.n_events, cl.n_local, cl.n_stored))
+                start += MS
+            del parts
+        shapes[mode] = shape
+        print(f"{mode}: close {med(t['close'])} ms", file=sys.stderr, flush=True)
+        res[mode + "_open_ms"], res[mode + "_close_ms"] = med(t["open"]), med(t["close"])
+        res[mode + "_close_ms_all"] = [round(x, 3) for x in t["close"]]
+        if mode == "staged":
+            res["staged_bytes"] = int(statistics.median(t["bytes"][-k:]))
+        if mode == "host":
+            res["host_groupby_ms"], res["host_h2d_ms"] = med(t["groupby"]), med(t["h2d"])
+            res["host_total_ms"] = round(res["host_groupby_ms"] + res["host_h2d_ms"] + res["host_close_ms"], 3)
+    res["same_results"] = shapes["device"] == shapes["staged"] == shapes["host"]
+    res["per_window_offers_popped_pending_batch_events_local_stored"] = shapes["device"][-k:]
+    extra = res["staged_close_ms"] - res["device_close_ms"]
+    res["staged_minus_device_ms"] = round(extra, 3)
+    res["staged_link_GBps"] = round(res["staged_bytes"] / extra / 1e6, 2) if extra > 0 else None
     print(json.dumps(res))
 
 
