@@ -64,6 +64,35 @@ __device__ __forceinline__ uint32_t dense_lat(const uint32_t* __restrict__ Wl, u
     else return Wl[(size_t)x * V + v];
 }
 
+// Row u of the matrix into LDS (row[v]: latency, +inf where there is no arc and at v == u), read
+// in 16-byte pieces: the row's memory span [u rs, u rs + rs), rs the row stride, walked in aligned
+// 4-word chunks, each element mapped back to its column (DCSR: a column at or past the diagonal
+// moves up by one).  The head and tail chunks, which reach outside the span, load word by word.
+template <int BLOCK, bool DCSR>
+__device__ __forceinline__ void load_row16(const uint32_t* __restrict__ Wl, uint32_t V, uint32_t u, uint32_t* row) {
+    const uint32_t rs = DCSR ? V - 1 : V, base = u * rs, a0 = base & ~3u;   // (V <= 4096: indices fit u32)
+    const uint32_t nch = (base + rs - a0 + 3u) >> 2;
+    for (uint32_t c = threadIdx.x; c < nch; c += BLOCK) {
+        const uint32_t p = a0 + 4u * c;
+        uint32_t w[4];
+        if (p >= base && p + 4u <= base + rs) {
+            const uint4 q = *reinterpret_cast<const uint4*>(Wl + p);
+            w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i) w[i] = p + i >= base && p + i < base + rs ? Wl[p + i] : kLat32Inf;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t e = p + i - base;   // (before the span: wraps past rs)
+            if (e >= rs) continue;
+            const uint32_t v = e + (DCSR && e >= u ? 1u : 0u);
+            row[v] = v == u ? kLat32Inf : w[i];
+        }
+    }
+    if (DCSR && threadIdx.x == 0) row[u] = kLat32Inf;   // (x, x) has no entry
+}
+
 // The detour selection shared by prune_rows and nearest_rows: the K nearest out-arcs of the row
 // held in LDS (row[v]: latency or +inf; mx: this thread's largest finite one, read without CMP
 // only; shg: the bin shift from the graph's largest arc latency, read with CMP only), left in
@@ -608,10 +637,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 64) void nearest_rows(   // 8 waves 
 // latencies, so a tight arc is never dropped whatever the candidate sets are, and ties keep the
 // arc.  The sums are guarded as there (a two-term sum that wraps or reaches +inf is no walk; the
 // three-term sum is formed in 64 bits).
-// Memory trips: the row (latencies, losses) and NN[u]; the first batch's gathers; NN[x] of the
-// S1 nodes, a half-wave per 256-B list; the lat(y, v) gathers of the pairs with d2[y] below
-// lat(u, v) (not SYM); the list write.  The lists are taken kPfRound = 16 kPfLists at a time,
-// kPfLists per half-wave (SYM 12: one round covers C2's longest S1, 151; 8 with the gather's
+// Memory trips: the row's latencies and NN[u]; the first batch's gathers; NN[x] of the S1 nodes,
+// 16 lanes per 256-B list, and with them the losses of the S1 arcs (no other arc needs its loss);
+// the lat(y, v) gathers of the pairs with d2[y] below lat(u, v) (not SYM); the list write.  The
+// row and the lists move 16 bytes per lane (load_row16, two NN entries per lane); the first
+// batch stays one dword per lane and detour: four consecutive columns per thread in one 16-byte
+// load measured slower, unaligned or as two aligned loads and a shift (routing item 2).
+// The lists are taken kPfRound = 16 kPfLists at a time, kPfLists / 2 per 16-lane group with two
+// entries per lane (SYM 12: one round covers C2's longest S1, 151; 8 with the gather's
 // registers), so registers stay bounded for any |S1|: every round lowers d2 first (last round
 // first, so round 0's lists are still in registers), then after one barrier every round is
 // tested, rounds past the first reading their lists again (L2 hits).  d2 is complete before the
@@ -625,24 +658,20 @@ template <bool DCSR, bool SYM>
 __global__ __launch_bounds__(kPfBlock, 8) void prune_fused(   // 8 waves per SIMD: four workgroups per CU
     const uint32_t* __restrict__ Wl, const float* __restrict__ Wp, uint32_t V, const uint2* __restrict__ NN,
     uint32_t* __restrict__ pbeg, uint32_t* __restrict__ pend, uint4* __restrict__ parcs) {
-    static_assert(kNear == 32 && (kPfFirst == 8 || kPfFirst == 16), "a half-wave per list");
-    constexpr int kPfLists = SYM ? 12 : 8;   // lists per half-wave and round (the gather form holds dy / lyv too)
+    static_assert(kNear == 32 && (kPfFirst == 8 || kPfFirst == 16), "16 lanes, two entries each, per list");
+    constexpr int kPfLists = SYM ? 12 : 8;   // list entries per lane and round (the gather form holds dy / lyv too)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint2* s1 = reinterpret_cast<uint2*>(smem);         // [V] S1(u): {v, lat(u, v)}, in arrival order
     uint32_t* d2 = reinterpret_cast<uint32_t*>(s1 + V); // [V] u's latency row, then the 2-hop row
-    float* prow = reinterpret_cast<float*>(d2 + V);     // [V] u's arc losses
+    float* prow = reinterpret_cast<float*>(d2 + V);     // [V] the S1 arcs' losses, by S1 slot
     uint32_t* drop = reinterpret_cast<uint32_t*>(prow + V);   // [V] S1 arc j falls
     uint32_t* nnx = drop + V;                           // NN[u]: nodes
     uint32_t* nna = nnx + kNear;                        //        latencies
     uint32_t* cnt = nna + kNear;                        // [0] |S1| [1] kept
     const uint32_t u = blockIdx.x, tid = threadIdx.x;
     const uint32_t rs = DCSR ? V - 1 : V;               // row stride of the matrix (V <= 4096: indices fit u32)
-    for (uint32_t v = tid; v < V; v += kPfBlock) {
-        const uint32_t w = v == u ? kLat32Inf : dense_lat<DCSR>(Wl, V, u, v);
-        d2[v] = w;
-        drop[v] = 0u;
-        if (w != kLat32Inf) prow[v] = Wp[(size_t)u * rs + v - (DCSR && v > u ? 1u : 0u)];
-    }
+    load_row16<kPfBlock, DCSR>(Wl, V, u, d2);
+    for (uint32_t v = tid; v < V; v += kPfBlock) drop[v] = 0u;
     if (tid < kNear) {
         const uint2 e = NN[(size_t)u * kNear + tid];
         nnx[tid] = e.x;
@@ -683,54 +712,80 @@ __global__ __launch_bounds__(kPfBlock, 8) void prune_fused(   // 8 waves per SIM
         }
     }
     __syncthreads();
-    constexpr uint32_t kPfRound = (kPfBlock / 32) * kPfLists;
+    // NN lists in 16-byte loads: two entries per lane, 16 lanes per 256-B list, four lists per
+    // wave instruction; kPfLists / 2 lists per 16-lane group hold the registers kPfLists did
+    static_assert(kPfLists % 2 == 0, "two entries per lane");
+    constexpr int kPfL4 = kPfLists / 2;
+    constexpr uint32_t kPfGroups = kPfBlock / 16, kPfRound = kPfGroups * kPfL4;
     const uint32_t n1 = cnt[0], rounds = (n1 + kPfRound - 1) / kPfRound;
-    const uint32_t hw = tid >> 5, sl = tid & 31;
-    uint2 pr[kPfLists];   // entry sl of this half-wave's lists: {y, lat(x, y)}
+    const uint32_t qw = tid >> 4, sl = tid & 15;
+    uint4 pr[kPfL4];   // entries 2 sl, 2 sl + 1 of this group's lists: {y, lat(x, y)} twice
     auto load_round = [&](uint32_t r) {
 #pragma unroll
-        for (int k = 0; k < kPfLists; ++k) {
-            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
-            pr[k] = make_uint2(0xFFFFFFFFu, kLat32Inf);
-            if (j < n1) pr[k] = NN[(size_t)s1[j].x * kNear + sl];
+        for (int k = 0; k < kPfL4; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * kPfGroups + qw;
+            pr[k] = make_uint4(0xFFFFFFFFu, kLat32Inf, 0xFFFFFFFFu, kLat32Inf);
+            if (j < n1) pr[k] = *reinterpret_cast<const uint4*>(NN + (size_t)s1[j].x * kNear + 2u * sl);
         }
     };
+    // the S1 arcs' losses (the row's other arcs never need theirs), by S1 slot: the first
+    // kPfBlock ride the first round's memory trip in a register, the rest (heavily tied rows) follow
+    float pl = 0.0f;
+    if (tid < n1) {
+        const uint32_t v = s1[tid].x;
+        pl = Wp[u * rs + v - (DCSR && v > u ? 1u : 0u)];
+    }
     for (uint32_t r = rounds; r-- > 0;) {   // d2 over the walks u -> x -> y
         load_round(r);
 #pragma unroll
-        for (int k = 0; k < kPfLists; ++k) {
-            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
+        for (int k = 0; k < kPfL4; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * kPfGroups + qw;
             if (j >= n1) continue;
-            const uint32_t y = pr[k].x, l1 = s1[j].y, t = l1 + pr[k].y;
-            if (y < V && y != u && pr[k].y != kLat32Inf && t >= l1 && t != kLat32Inf) atomicMin(&d2[y], t);
+            const uint32_t l1 = s1[j].y;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t y = h ? pr[k].z : pr[k].x, l = h ? pr[k].w : pr[k].y, t = l1 + l;
+                if (y < V && y != u && l != kLat32Inf && t >= l1 && t != kLat32Inf) atomicMin(&d2[y], t);
+            }
         }
+    }
+    if (tid < n1) prow[tid] = pl;
+    for (uint32_t j = kPfBlock + tid; j < n1; j += kPfBlock) {
+        const uint32_t v = s1[j].x;
+        prow[j] = Wp[u * rs + v - (DCSR && v > u ? 1u : 0u)];
     }
     __syncthreads();
     for (uint32_t r = 0; r < rounds; ++r) {   // (u, v = list j's node) against u ~> y -> v
         if (r) load_round(r);
         uint32_t dy[kPfLists], lyv[kPfLists];
 #pragma unroll
-        for (int k = 0; k < kPfLists; ++k) {
-            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
-            dy[k] = kLat32Inf;
-            lyv[k] = kLat32Inf;
-            if (j >= n1) continue;
-            const uint2 e = s1[j];
-            const uint32_t y = pr[k].x;
-            if (y >= V || y == u || y == e.x) continue;
-            const uint32_t d = d2[y];
-            // (a walk no shorter than the arc before its last step cannot beat it: no load)
-            if (d < e.y) {
-                dy[k] = d;
-                // SYM (undirected graphs): lat(y, v) = lat(v, y), which NN[v] holds -- no gather
-                lyv[k] = SYM ? pr[k].y : Wl[y * rs + e.x - (DCSR && e.x > y ? 1u : 0u)];
+        for (int k = 0; k < kPfL4; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * kPfGroups + qw;
+            const uint2 e = j < n1 ? s1[j] : make_uint2(0u, 0u);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                dy[2 * k + h] = kLat32Inf;
+                lyv[2 * k + h] = kLat32Inf;
+                if (j >= n1) continue;
+                const uint32_t y = h ? pr[k].z : pr[k].x;
+                if (y >= V || y == u || y == e.x) continue;
+                const uint32_t d = d2[y];
+                // (a walk no shorter than the arc before its last step cannot beat it: no load)
+                if (d < e.y) {
+                    dy[2 * k + h] = d;
+                    // SYM (undirected graphs): lat(y, v) = lat(v, y), which NN[v] holds -- no gather
+                    lyv[2 * k + h] = SYM ? (h ? pr[k].w : pr[k].y) : Wl[y * rs + e.x - (DCSR && e.x > y ? 1u : 0u)];
+                }
             }
         }
 #pragma unroll
-        for (int k = 0; k < kPfLists; ++k) {
-            const uint32_t j = r * kPfRound + (uint32_t)k * (kPfBlock / 32) + hw;
-            if (j < n1 && lyv[k] != kLat32Inf && dy[k] != kLat32Inf && (uint64_t)dy[k] + lyv[k] < (uint64_t)s1[j].y)
-                drop[j] = 1u;
+        for (int k = 0; k < kPfL4; ++k) {
+            const uint32_t j = r * kPfRound + (uint32_t)k * kPfGroups + qw;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t d = dy[2 * k + h], l = lyv[2 * k + h];
+                if (j < n1 && l != kLat32Inf && d != kLat32Inf && (uint64_t)d + l < (uint64_t)s1[j].y) drop[j] = 1u;
+            }
         }
     }
     __syncthreads();
@@ -738,7 +793,7 @@ __global__ __launch_bounds__(kPfBlock, 8) void prune_fused(   // 8 waves per SIM
     for (uint32_t j = tid; j < n1; j += kPfBlock) {
         if (drop[j]) continue;
         const uint2 e = s1[j];
-        parcs[at + atomicAdd(&cnt[1], 1u)] = make_uint4(e.x, e.y, __float_as_uint(one_minus(prow[e.x])), 0u);
+        parcs[at + atomicAdd(&cnt[1], 1u)] = make_uint4(e.x, e.y, __float_as_uint(one_minus(prow[j])), 0u);
     }
     __syncthreads();
     const uint32_t n2 = cnt[1], np = (n2 + kPad2 - 1) / kPad2 * kPad2;

@@ -164,6 +164,45 @@ __device__ __forceinline__ void expand_queue_nr(const uint32_t* q, uint32_t qn, 
     }
 }
 
+// The table's row in 16-byte stores, four columns per thread: two for the latencies, one for the
+// losses (row_emit writes an 8-byte and a 4-byte one per column), non-temporal as there.  For the
+// identity used set with n_used % 4 == 0 and both output rows 16-byte aligned; the caller sends
+// every other case, and the next hops, through row_emit.  The diagonal and an unreachable column
+// are handled per element, as row_emit does.
+typedef uint64_t u64x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+template <int BLOCK>
+__device__ __forceinline__ void row_emit4(const uint64_t* lab, uint32_t n_used, uint32_t row, size_t orow,
+                                          const uint64_t* __restrict__ diag_lat, const float* __restrict__ diag_loss,
+                                          uint64_t* __restrict__ out_lat, float* __restrict__ out_loss,
+                                          unsigned long long* __restrict__ unreach) {
+    for (uint32_t j0 = 4u * threadIdx.x; j0 < n_used; j0 += 4u * BLOCK) {
+        uint64_t k[4], l[4];
+        float p[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) k[i] = ld_lab<false>(&lab[j0 + i]);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t j = j0 + i;
+            if (j == row) {
+                l[i] = diag_lat[j];
+                p[i] = diag_loss[j];
+            } else if (k[i] == kKeyInf) {
+                atomicMin(unreach, (unsigned long long)((uint64_t)row * n_used + j));
+                l[i] = ~0ull;
+                p[i] = 0.0f;
+            } else {
+                l[i] = key_lat(k[i]);
+                p[i] = key_loss(k[i]);
+            }
+        }
+        u64x2_t* ol = reinterpret_cast<u64x2_t*>(out_lat + orow + j0);
+        __builtin_nontemporal_store(u64x2_t{l[0], l[1]}, ol);
+        __builtin_nontemporal_store(u64x2_t{l[2], l[3]}, ol + 1);
+        __builtin_nontemporal_store(f32x4_t{p[0], p[1], p[2], p[3]}, reinterpret_cast<f32x4_t*>(out_loss + orow + j0));
+    }
+}
+
 template <int BLOCK, int G, int PADR>
 __device__ __forceinline__ void sssp_row_shadow(
     uint64_t* lab, uint32_t* ctl, uint32_t* wq, uint2* rng, const uint32_t* __restrict__ abeg,
@@ -178,10 +217,20 @@ __device__ __forceinline__ void sssp_row_shadow(
     const uint32_t grp = lane / G, gl = lane % G;
     uint32_t* q = wq + wave * kQStride;
     const uint32_t src = used ? used[row] : row;
-    for (uint32_t v = tid; v < V; v += BLOCK) {
-        lab[v] = v == src ? 0ull : kKeyInf;   // PathProperties::default() = (0 ns, 0.0)
-        rng[v] = make_uint2(abeg[v], aend[v]);
+    // the arc ranges, four nodes per 16-byte load when both range arrays are 16-byte aligned (the
+    // prune's are when V % 4 == 0); every row reads the same arrays
+    const bool rng16 = ((reinterpret_cast<uintptr_t>(abeg) | reinterpret_cast<uintptr_t>(aend)) & 15u) == 0;
+    const uint32_t v16 = rng16 ? V & ~3u : 0u;
+    for (uint32_t v = 4u * tid; v < v16; v += 4u * BLOCK) {
+        const uint4 b = *reinterpret_cast<const uint4*>(abeg + v), e = *reinterpret_cast<const uint4*>(aend + v);
+        rng[v] = make_uint2(b.x, e.x);
+        rng[v + 1] = make_uint2(b.y, e.y);
+        rng[v + 2] = make_uint2(b.z, e.z);
+        rng[v + 3] = make_uint2(b.w, e.w);
     }
+    for (uint32_t v = v16 + tid; v < V; v += BLOCK) rng[v] = make_uint2(abeg[v], aend[v]);
+    // PathProperties::default() = (0 ns, 0.0)
+    for (uint32_t v = tid; v < V; v += BLOCK) lab[v] = v == src ? 0ull : kKeyInf;
     if (tid < 64) lab[V + tid] = 0;   // scratch labels: no candidate improves them
     if (tid == 0) ctl[1] = ctl[2] = ctl[3] = kLat32Inf;
     __syncthreads();
@@ -265,8 +314,12 @@ __device__ __forceinline__ void sssp_row_shadow(
         atomicAdd(&stats[0], (unsigned long long)expanded);
         if (wave == 0) atomicAdd(&stats[1], (unsigned long long)sweeps);
     }
-    row_emit<BLOCK, false>(lab, pred, abeg, aend, arcs, V, used, n_used, src, row, orow, diag_lat, diag_loss, out_lat,
-                           out_loss, unreach, nh_out, nullptr, 0u);
+    if (!used && !nh_out && n_used % 4 == 0 &&
+        ((reinterpret_cast<uintptr_t>(out_lat + orow) | reinterpret_cast<uintptr_t>(out_loss + orow)) & 15u) == 0)
+        row_emit4<BLOCK>(lab, n_used, row, orow, diag_lat, diag_loss, out_lat, out_loss, unreach);
+    else
+        row_emit<BLOCK, false>(lab, pred, abeg, aend, arcs, V, used, n_used, src, row, orow, diag_lat, diag_loss,
+                               out_lat, out_loss, unreach, nh_out, nullptr, 0u);
 }
 
 template <int BLOCK, int G, int PADR>
