@@ -170,19 +170,24 @@ struct OutboundState {
     bool ready = false;
 };
 
-// shd_offers_group (offers.hip): the worker threads' staged offers grouped by host into the
-// outbound stage's columns -- the runs as uploaded (or copied out of the pinned stages), each
-// host's run, the records (copy path only), and the grouped columns handed out (engine-owned,
-// valid until the next group).
-struct OffersState {
+// The grouping of staged runs by host (stage_group.hip), one per staged entry point: the runs as
+// uploaded (or copied out of the pinned stages) and each host's run.
+struct StageGroupState {
     DevBuf runh, runc, runo, rstg;   // per run: host, count, first record in stage order, stage (zero-copy)
-    DevBuf hrun, hcnt;               // per host: its run (+1), its offers
-    DevBuf rec;                      // the records of every stage, stage after stage (copy path)
+    DevBuf hrun, hcnt;               // per host: its run (+1), its records
     DevBuf tab;                      // zero-copy: the stage table, and its pinned source
     PinBuf tab_pin;
-    DevBuf red;                      // the two check words
-    DevBuf d_off, d_time, d_prio, d_sock, d_size, d_pay, d_dst, d_pkt;
+    DevBuf red;                      // four words: the two checks, then two of the caller's
     ScanScratch scan;
+};
+
+// shd_offers_group (offers.hip): the worker threads' staged offers grouped by host into the
+// outbound stage's columns -- the grouping, the records (copy path only), and the grouped columns
+// handed out (engine-owned, valid until the next group).
+struct OffersState {
+    StageGroupState grp;
+    DevBuf rec;                      // the records of every stage, stage after stage (copy path)
+    DevBuf d_off, d_time, d_prio, d_sock, d_size, d_pay, d_dst, d_pkt;
 };
 
 // The packet ledger (ledger.hip): each batch's (total size, packet id) per packet, kept on the
@@ -280,21 +285,20 @@ struct RelayState {
     DevBuf xs_st;
     bool xs_st_dirty = false;
     // shd_relay_flush (flush.hip): the round's draws came from the CPU (top 32 bits in `draws`), the
-    // staged runs and records as uploaded, the send permutation (grouped <-> stage order) and the
-    // packed outputs
+    // grouping of the staged runs (fl_grp), the records as uploaded (fl_send, copy path only), the
+    // send permutation (grouped <-> stage order) and the packed outputs
     bool cpu_draws = false;
     // a sharded shd_relay_flush round: event ids leave the device relative to their source host's
     // first id of the round (a receiver does not hold the other ranks' hosts' ids)
     bool rel_ids = false;
     DevBuf fl_goff;   // the flush's grouped offsets over every host (sharded: all ranks' hosts)
+    StageGroupState fl_grp;
     // a one-context flush round: pipeline 7's bin sort writes the compact event records here
     // (fl_direct says it did; the other pipelines leave the arrays for fl_events16)
-    DevBuf fl_tab, fl_rstg;   // zero-copy staging: the stage table, each run's stage
-    PinBuf fl_tab_pin;
     void* fl_ev_out = nullptr;
     uint32_t fl_b12 = 0;
     bool fl_direct = false;
-    DevBuf fl_runh, fl_runc, fl_runo, fl_hrun, fl_hcnt, fl_send, fl_perm, fl_inv, fl_st2, fl_ev16;
+    DevBuf fl_send, fl_perm, fl_inv, fl_st2, fl_ev16;
 };
 
 struct PreparedGraph {

@@ -12,16 +12,16 @@
 //   the reference; the top 32 bits decide `chance >= reliability` exactly for every reliability
 //   1f32 - loss (relay_priv.h draw_drops).
 // The device turns the runs into the grouped layout the pipelines take (src_off, one contiguous
-// range per host in host order), runs the round with those draws (the device streams are left
+// range per host in host order; the grouping is stage_group.h's, shared with shd_offers_group, the
+// gather this unit's), runs the round with those draws (the device streams are left
 // untouched), and writes back per send a 2-bit status in stage order, and per event a 16-byte
 // record {deliver - round_end, src host, event id - the host's first id of the round, send index
 // in stage order} grouped by destination in EventQueue order (event.rs:84-155).
 #include <algorithm>
-#include <cstring>
 
 #include "pin_view.h"
 #include "relay_priv.h"
-#include "scan.h"
+#include "stage_group.h"
 
 namespace shd {
 
@@ -29,93 +29,25 @@ struct Send12 {
     uint32_t time_off, dst, draw_hi;
 };
 static_assert(sizeof(Send12) == sizeof(shd_send12), "12-byte staged send");
+constexpr uint32_t kSendWords = sizeof(Send12) / 4;
 
-// per run: its host's run index (+1); a second run of one host is an error (red[0]), as is a
-// host outside the relay (red[1])
-__global__ __launch_bounds__(256) void fl_runs(uint32_t n_runs, const uint32_t* __restrict__ run_host,
-                                               uint32_t n_hosts, uint32_t* __restrict__ hrun,
-                                               unsigned long long* __restrict__ red) {
-    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_runs) return;
-    const uint32_t h = run_host[r];
-    if (h >= n_hosts) {
-        atomicMin(&red[1], (unsigned long long)r);
-        return;
-    }
-    if (atomicExch(&hrun[h], r + 1) != 0) atomicMin(&red[0], (unsigned long long)h);
-}
-
-// Zero-copy staging: when every staging buffer is pinned host memory the device reads it where it
-// lies (a device view of the pinned pages) instead of one copy per buffer -- at C5 three copies per
-// worker thread, each with ~11 us of launch gap, plus the re-read of the uploaded sends.
-struct FlStage {
-    const uint32_t* rh;    // device views of the stage's run_host / run_count / sends
-    const uint32_t* rc;
-    const Send12* sd;
-    uint64_t send_base;    // the stage's first send in stage order
-    uint32_t run_base, n_runs;
-};
-
-// fl_runs on the staged runs themselves: each run's host and count (copied to the device arrays
-// the scans read) and its stage
-__global__ __launch_bounds__(256) void fl_runs_zc(uint32_t n_runs, const FlStage* __restrict__ st, uint32_t n_stages,
-                                                  uint32_t n_hosts, uint32_t* __restrict__ runh,
-                                                  uint32_t* __restrict__ runc, uint32_t* __restrict__ rstage,
-                                                  uint32_t* __restrict__ hrun, unsigned long long* __restrict__ red) {
-    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_runs) return;
-    uint32_t lo = 0, hi = n_stages;   // the last stage whose first run is <= r (stages without runs skipped)
-    while (hi - lo > 1) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (st[m].run_base <= r) lo = m; else hi = m;
-    }
-    while (lo + 1 < n_stages && (st[lo].n_runs == 0 || r - st[lo].run_base >= st[lo].n_runs)) ++lo;
-    const uint32_t i = r - st[lo].run_base, h = st[lo].rh[i];
-    runh[r] = h;
-    runc[r] = st[lo].rc[i];
-    rstage[r] = lo;
-    if (h >= n_hosts) {
-        atomicMin(&red[1], (unsigned long long)r);
-        return;
-    }
-    if (atomicExch(&hrun[h], r + 1) != 0) atomicMin(&red[0], (unsigned long long)h);
-}
-
-// per host: its send count (0 without a run); entry n_hosts is 0 so one scan gives src_off[0..H]
-__global__ __launch_bounds__(256) void fl_host_counts(uint32_t n_hosts, const uint32_t* __restrict__ hrun,
-                                                      const uint32_t* __restrict__ run_count,
-                                                      uint32_t* __restrict__ hcnt) {
-    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h > n_hosts) return;
-    const uint32_t r = h < n_hosts ? hrun[h] : 0u;
-    hcnt[h] = r ? run_count[r - 1] : 0u;
-}
-
-// one wave per host: its run's records into the grouped arrays the pipelines read, the permutation
-// both ways (grouped position <-> send index in stage order).  Under a communicator every rank
-// groups every host's sends (the permutation covers all of them) but writes the arrays of its own
-// hosts [lo, hi) only, from position src_off[lo] on.
-__global__ __launch_bounds__(256) void fl_gather(uint32_t n_hosts, const uint32_t* __restrict__ hrun,
-                                                 const uint32_t* __restrict__ run_off,
-                                                 const uint32_t* __restrict__ src_off, const Send12* __restrict__ in,
+// one wave per host: its run's records (stage_run) into the grouped arrays the pipelines read, the
+// permutation both ways (grouped position <-> send index in stage order).  Under a communicator
+// every rank groups every host's sends (the permutation covers all of them) but writes the arrays
+// of its own hosts [lo, hi) only, from position src_off[lo] on.
+__global__ __launch_bounds__(256) void fl_gather(StageRuns g, uint32_t n_hosts, const uint32_t* __restrict__ src_off,
                                                  uint64_t time_base, uint64_t* __restrict__ send_time,
                                                  uint32_t* __restrict__ dst_host, uint32_t* __restrict__ payload,
                                                  uint32_t* __restrict__ draws, uint32_t* __restrict__ perm,
-                                                 uint32_t* __restrict__ inv, uint32_t lo, uint32_t hi,
-                                                 const FlStage* __restrict__ st, const uint32_t* __restrict__ rstage) {
+                                                 uint32_t* __restrict__ inv, uint32_t lo, uint32_t hi) {
     const uint32_t h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (h >= n_hosts) return;
-    const uint32_t r = hrun[h];
-    if (!r) return;
-    const uint32_t from = run_off[r - 1], to = src_off[h], cnt = src_off[h + 1] - to;
+    RunRecords run;
+    if (!stage_run(g, src_off, h, lane, run)) return;
+    const uint32_t from = run.from, to = run.to, cnt = run.cnt;
     const bool own = h >= lo && h < hi;
     const uint32_t base = src_off[lo];
-    // the run's sends: in the uploaded copy, or (zero-copy) in its stage's pinned buffer
-    const Send12* rs = in + from;
-    if (st) {
-        const FlStage& S = st[rstage[r - 1]];
-        rs = S.sd + (from - S.send_base);
-    }
+    const Send12* rs = reinterpret_cast<const Send12*>(run.rec);
     for (uint32_t k = lane; k < cnt; k += 64) {
         const uint32_t p = to + k;
         perm[p] = from + k;
@@ -223,28 +155,15 @@ shd_status shd_relay_flush(shd_ctx* ctx, const shd_stage* stages, uint32_t n_sta
     if (!R.ready) return SHD_ERR_STATE;
     if (R.sharded && (!R.x_words.p || !R.xs_pin.p)) return SHD_ERR_STATE;   // set up before the communicator
     // host-side shape checks (each stage's runs cover exactly its records)
-    uint64_t n = 0, n_runs = 0;
-    for (uint32_t k = 0; k < n_stages; ++k) {
-        const shd_stage& S = stages[k];
-        if (S.n_runs && (!S.run_host || !S.run_count)) return SHD_ERR_INVALID;
-        if (S.n_sends && !S.sends) return SHD_ERR_INVALID;
-        uint64_t c = 0;
-        for (uint32_t r = 0; r < S.n_runs; ++r) c += S.run_count[r];
-        if (c != S.n_sends) return SHD_ERR_INVALID;
-        n += S.n_sends;
-        n_runs += S.n_runs;
-    }
+    std::vector<StageView> views(n_stages);
+    for (uint32_t k = 0; k < n_stages; ++k)
+        views[k] = StageView{stages[k].n_runs, stages[k].run_host, stages[k].run_count, stages[k].n_sends, stages[k].sends};
+    uint64_t n = 0;
+    if (!stages_ok(views.data(), n_stages, nullptr, &n)) return SHD_ERR_INVALID;
     const uint32_t H = R.n_hosts;
-    if (n >= (1ull << 32) || n_runs >= (1ull << 32)) return SHD_ERR_INVALID;
     SHD_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t nn = std::max<uint64_t>(n, 1), nr = std::max<uint64_t>(n_runs, 1);
-    SHD_TRY(R.fl_runh.ensure(nr * 4));
-    SHD_TRY(R.fl_runc.ensure(nr * 4));
-    SHD_TRY(R.fl_runo.ensure(nr * 4));
-    SHD_TRY(R.fl_hrun.ensure((size_t)(H + 1) * 4));
-    SHD_TRY(R.fl_hcnt.ensure((size_t)(H + 1) * 4));
-    SHD_TRY(R.fl_send.ensure(nn * 12));
+    const size_t nn = std::max<uint64_t>(n, 1);
     SHD_TRY(R.fl_perm.ensure(nn * 4));
     SHD_TRY(R.fl_inv.ensure(nn * 4));
     SHD_TRY(R.fl_st2.ensure(nn / 4 + 1));
@@ -265,84 +184,24 @@ shd_status shd_relay_flush(shd_ctx* ctx, const shd_stage* stages, uint32_t n_sta
     // under a communicator: this rank's hosts [lo, hi) (the stages hold every rank's hosts)
     uint32_t lo = 0, hi = H;
     if (R.sharded) shard_range(H, ctx->comm->size, ctx->comm->rank, &lo, &hi);
-    // 1. the staging buffers: read where they lie when all are pinned (zero-copy), else copied stage
-    //    after stage (pinned host memory -- shd_host_alloc -- moves at the link's rate; pageable
-    //    memory is staged by the runtime)
-    std::vector<FlStage> tab(n_stages);
-    bool zc = n_stages > 0 && !ctx->knobs.on(K_FLUSH_COPY);
-    {
-        uint64_t at = 0;
-        uint32_t ar = 0;
-        for (uint32_t k = 0; k < n_stages && zc; ++k) {
-            const shd_stage& S = stages[k];
-            FlStage& T = tab[k];
-            T.rh = static_cast<const uint32_t*>(S.n_runs ? dev_view(S.run_host) : nullptr);
-            T.rc = static_cast<const uint32_t*>(S.n_runs ? dev_view(S.run_count) : nullptr);
-            T.sd = static_cast<const Send12*>(S.n_sends ? dev_view(S.sends) : nullptr);
-            if ((S.n_runs && (!T.rh || !T.rc)) || (S.n_sends && !T.sd)) zc = false;
-            T.send_base = at;
-            T.run_base = ar;
-            T.n_runs = S.n_runs;
-            at += S.n_sends;
-            ar += S.n_runs;
-        }
-    }
-    if (zc) {
-        SHD_TRY(R.fl_tab.ensure((size_t)n_stages * sizeof(FlStage)));
-        SHD_TRY(R.fl_tab_pin.ensure((size_t)n_stages * sizeof(FlStage)));
-        SHD_TRY(R.fl_rstg.ensure(nr * 4));
-        std::memcpy(R.fl_tab_pin.p, tab.data(), (size_t)n_stages * sizeof(FlStage));
-        SHD_HIP(hipMemcpyAsync(R.fl_tab.p, R.fl_tab_pin.p, (size_t)n_stages * sizeof(FlStage), hipMemcpyHostToDevice, s));
-    }
-    if (!zc) {
-        uint64_t at = 0, ar = 0;
-        for (uint32_t k = 0; k < n_stages; ++k) {
-            const shd_stage& S = stages[k];
-            if (S.n_runs) {
-                SHD_HIP(hipMemcpyAsync(R.fl_runh.as<uint32_t>() + ar, S.run_host, (size_t)S.n_runs * 4,
-                                       hipMemcpyHostToDevice, s));
-                SHD_HIP(hipMemcpyAsync(R.fl_runc.as<uint32_t>() + ar, S.run_count, (size_t)S.n_runs * 4,
-                                       hipMemcpyHostToDevice, s));
-            }
-            if (S.n_sends)
-                SHD_HIP(hipMemcpyAsync(R.fl_send.as<char>() + at * 12, S.sends, S.n_sends * 12, hipMemcpyHostToDevice, s));
-            at += S.n_sends;
-            ar += S.n_runs;
-        }
-    }
-    // 2. runs -> hosts, per-host counts, the grouped offsets, the gather
-    unsigned long long* red = R.red.as<unsigned long long>();
-    SHD_HIP(hipMemsetAsync(R.fl_hrun.p, 0, (size_t)(H + 1) * 4, s));
-    SHD_HIP(hipMemsetAsync(red, 0xFF, 16, s));
-    if (n_runs) {
-        if (zc)
-            fl_runs_zc<<<div_up(n_runs, 256), 256, 0, s>>>((uint32_t)n_runs, R.fl_tab.as<FlStage>(), n_stages, H,
-                                                            R.fl_runh.as<uint32_t>(), R.fl_runc.as<uint32_t>(),
-                                                            R.fl_rstg.as<uint32_t>(), R.fl_hrun.as<uint32_t>(), red);
-        else
-            fl_runs<<<div_up(n_runs, 256), 256, 0, s>>>((uint32_t)n_runs, R.fl_runh.as<uint32_t>(), H,
-                                                         R.fl_hrun.as<uint32_t>(), red);
-        SHD_TRY(scan_excl2(R.scan, R.fl_runc.as<uint32_t>(), R.fl_runo.as<uint32_t>(), nullptr, nullptr, n_runs, s));
-    }
-    fl_host_counts<<<div_up((uint64_t)H + 1, 256), 256, 0, s>>>(H, R.fl_hrun.as<uint32_t>(), R.fl_runc.as<uint32_t>(),
-                                                                R.fl_hcnt.as<uint32_t>());
+    // 1. the grouping over every host (stage_group.h; the FLUSH_COPY knob forces the copies)
     uint32_t* goff = R.sharded ? R.fl_goff.as<uint32_t>() : R.pk_off.as<uint32_t>();   // grouped offsets, all hosts
-    SHD_TRY(scan_excl2(R.scan, R.fl_hcnt.as<uint32_t>(), goff, nullptr, nullptr, (uint64_t)H + 1, s));
+    StageRuns g;
+    SHD_TRY(stage_group(R.fl_grp, views.data(), n_stages, kSendWords, 0, H, ctx->knobs.on(K_FLUSH_COPY), R.fl_send, goff,
+                        s, &g));
+    // 2. the gather
     if (n)
-        fl_gather<<<div_up(H, 4), 256, 0, s>>>(H, R.fl_hrun.as<uint32_t>(), R.fl_runo.as<uint32_t>(), goff,
-                                                R.fl_send.as<Send12>(), time_base, R.pk_time.as<uint64_t>(),
-                                                R.pk_dst.as<uint32_t>(), R.pk_pay.as<uint32_t>(), R.draws.as<uint32_t>(),
-                                                R.fl_perm.as<uint32_t>(), R.fl_inv.as<uint32_t>(), lo, hi,
-                                                zc ? R.fl_tab.as<FlStage>() : nullptr,
-                                                zc ? R.fl_rstg.as<uint32_t>() : nullptr);
+        fl_gather<<<div_up(H, 4), 256, 0, s>>>(g, H, goff, time_base, R.pk_time.as<uint64_t>(), R.pk_dst.as<uint32_t>(),
+                                                R.pk_pay.as<uint32_t>(), R.draws.as<uint32_t>(),
+                                                R.fl_perm.as<uint32_t>(), R.fl_inv.as<uint32_t>(), lo, hi);
     if (R.sharded)
-        fl_rebase<<<div_up((uint64_t)(hi - lo) + 1, 256), 256, 0, s>>>(goff, lo, hi - lo, R.pk_off.as<uint32_t>(), red);
+        fl_rebase<<<div_up((uint64_t)(hi - lo) + 1, 256), 256, 0, s>>>(goff, lo, hi - lo, R.pk_off.as<uint32_t>(), g.red);
     SHD_HIP(hipGetLastError());
     // h_pin words 32-35: the checks (and, sharded, this rank's grouped range).  Under a communicator a
     // failed check is this rank's alone: the flush returns before the round's collectives, as a call
     // with invalid arguments would, on whichever ranks see the bad runs (every rank sees the same
     // stages, so all of them do).
-    SHD_TRY(readback(ctx, s, 32, red, R.sharded ? 32 : 16));
+    SHD_TRY(readback(ctx, s, 32, g.red, R.sharded ? 32 : 16));
     if (ctx->h_pin[33] != ~0ull) return SHD_ERR_NO_HOST;   // a run of a host the relay does not have
     if (ctx->h_pin[32] != ~0ull) return SHD_ERR_INVALID;   // a host with two runs (two threads, or split)
     const uint64_t base = R.sharded ? ctx->h_pin[34] : 0, n_own = R.sharded ? ctx->h_pin[35] - ctx->h_pin[34] : n;

@@ -1,7 +1,8 @@
-// The staged offer record of shd_offers_group (offers.hip) and the host-side check of the stages'
-// shape.  No HIP type in here: tests/offer_stage_main.cpp compiles this header alone, with the
-// address and undefined-behaviour sanitizers, and tests/test_offers.py runs it against the numpy
-// group-by; the kernels read records through the same constants and the same decode.
+// The staged offer record of shd_offers_group (offers.hip) and the host-side check of its
+// arguments (the stages' shape is stage_shape.h's).  No HIP type in here:
+// tests/offer_stage_main.cpp compiles this header alone, with the address and undefined-behaviour
+// sanitizers, and tests/test_offers.py runs it against the numpy group-by; the kernels read
+// records through the same constants and the same decode.
 //
 // A stage is one worker thread's buffer at the round barrier: runs (host, count) and, run after
 // run, the hosts' offers in the order each host made them -- `offer_words` u32 words per offer:
@@ -9,6 +10,10 @@
 //   5 reserved   6, 7 the d_prio key, low then high   8, 9 d_sock, low then high (width 10 only)
 #pragma once
 #include <stdint.h>
+
+#include <vector>
+
+#include "stage_shape.h"
 
 #if defined(__HIP__)   // a HIP unit: the kernels decode with the same function
 #define SHD_OFFER_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
@@ -40,10 +45,20 @@ SHD_OFFER_HD Offer offer_decode(const uint32_t* w, uint32_t words, uint64_t time
     return o;
 }
 
-// The stages' shape, checked on the host before anything is uploaded: a width the discipline takes
-// (need_sock: one of the two socket disciplines, which have no 8-word form), no NULL array where a
-// count is not zero, every stage's run counts adding up to its stage_offers, fewer than 2^32 runs
-// and offers in all.  Reads the run counts only; false: refused, the totals are not written.
+// The stages as stage_shape.h's neutral views (what the shared check and stage_group take); the
+// five tables hold n_stages entries each.
+inline std::vector<StageView> offer_stage_views(uint32_t n_stages, const uint32_t* stage_runs,
+                                                const uint32_t* const* run_host, const uint32_t* const* run_count,
+                                                const uint64_t* stage_offers, const uint32_t* const* offers) {
+    std::vector<StageView> v(n_stages);
+    for (uint32_t k = 0; k < n_stages; ++k)
+        v[k] = StageView{stage_runs[k], run_host[k], run_count[k], stage_offers[k], offers[k]};
+    return v;
+}
+
+// A width the discipline takes (need_sock: one of the two socket disciplines, which have no 8-word
+// form), the five tables present, and the stages' shape (stages_ok).  false: refused, the totals
+// are not written.
 inline bool offer_stages_ok(uint32_t n_stages, const uint32_t* stage_runs, const uint32_t* const* run_host,
                             const uint32_t* const* run_count, const uint64_t* stage_offers,
                             const uint32_t* const* offers, uint32_t offer_words, bool need_sock, uint64_t* n_runs,
@@ -51,23 +66,8 @@ inline bool offer_stages_ok(uint32_t n_stages, const uint32_t* stage_runs, const
     if (offer_words != kOfferWords && offer_words != kOfferWordsSock) return false;
     if (need_sock && offer_words != kOfferWordsSock) return false;
     if (n_stages && (!stage_runs || !run_host || !run_count || !stage_offers || !offers)) return false;
-    uint64_t nr = 0, no = 0;
-    for (uint32_t k = 0; k < n_stages; ++k) {   // the totals first: no array is read for a call too large
-        if (stage_offers[k] >= (1ull << 32)) return false;
-        nr += stage_runs[k];
-        no += stage_offers[k];
-        if (nr >= (1ull << 32) || no >= (1ull << 32)) return false;
-    }
-    for (uint32_t k = 0; k < n_stages; ++k) {
-        if (stage_runs[k] && (!run_host[k] || !run_count[k])) return false;
-        if (stage_offers[k] && !offers[k]) return false;
-        uint64_t c = 0;
-        for (uint32_t r = 0; r < stage_runs[k]; ++r) c += run_count[k][r];
-        if (c != stage_offers[k]) return false;
-    }
-    if (n_runs) *n_runs = nr;
-    if (n_offers) *n_offers = no;
-    return true;
+    return stages_ok(offer_stage_views(n_stages, stage_runs, run_host, run_count, stage_offers, offers).data(), n_stages,
+                     n_runs, n_offers);
 }
 
 }  // namespace shd

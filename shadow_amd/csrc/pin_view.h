@@ -1,4 +1,5 @@
-// Zero-copy staging (flush.hip, offers.hip): the device's view of a caller's pinned host buffer.
+// Zero-copy staging (stage_group.hip) and zero-copy outputs (flush.hip): the device's view of a
+// caller's pinned host buffer.
 #pragma once
 #include "common.h"
 

@@ -102,6 +102,105 @@ def test_flush_many_hosts_runs(engine):
     _check(fr, o, st, np.zeros(H, np.uint64), start + ra)
 
 
+EDGES = [0, 1, 0, 63, 64, 0, 65, 200]   # sends of neighbouring hosts: the wave-stride loop's edges
+NO_RUN = (2, 5)                         # ... hosts 2 and 5 without a run, host 0 a run of 0
+
+
+def _edge_round(start, ra, seed):
+    """8 hosts with EDGES sends each, staged by three threads of which the middle one is idle; the
+    zero-count runs of the NO_RUN hosts are dropped (host 0 keeps its run of 0)."""
+    from shadow_amd import synth
+    rng = np.random.default_rng(seed)
+    H, n = len(EDGES), sum(EDGES)
+    src = np.repeat(np.arange(H, dtype=np.uint32), EDGES)
+    dst = rng.integers(0, H - 1, n, dtype=np.uint32)
+    dst = dst + (dst >= src).astype(np.uint32)   # among the other hosts
+    off = np.zeros(H + 1, np.uint32)
+    np.cumsum(EDGES, out=off[1:])
+    t = rng.integers(start, start + ra, n, dtype=np.uint64)
+    t = t[np.lexsort((t, src))]                  # each host's sends in time order
+    b = synth.PacketBatch(off, t, dst, rng.choice(np.array([0, 1, 1448], np.uint32), n))
+    st = synth.stage_round(b, 2, start, seed=seed)
+    for k in range(2):
+        keep = ~np.isin(st.run_host[k], NO_RUN)
+        st.run_host[k], st.run_count[k] = st.run_host[k][keep], st.run_count[k][keep]
+    for a, empty in ((st.run_host, np.zeros(0, np.uint32)), (st.run_count, np.zeros(0, np.uint32)),
+                     (st.sends, np.zeros((0, 3), np.uint32))):
+        a.insert(1, empty)
+    hosts = np.concatenate(st.run_host)
+    assert 0 in hosts and not np.isin(NO_RUN, hosts).any() and all(len(h) for h in (st.run_host[0], st.run_host[2]))
+    return b, st
+
+
+@pytest.mark.parametrize("buffers", ["pinned", "pageable", "pinned-copy"])
+def test_flush_edge_shapes(engine, knob, buffers):
+    """The grouping's small shapes under the flush (the offers' are tests/test_offers_gpu.py's): run
+    lengths 0, 1, 63, 64, 65 and 200, hosts without a run, an idle thread; stages read in place,
+    copied because they are pageable, and copied because FLUSH_COPY says so."""
+    from shadow_amd.relay import PinnedStages, Relay
+    H, start, ra = len(EDGES), 10**9, 10**6
+    lat, loss, host_node, rng0 = _case(H, 4, 31)
+    knob("FLUSH_COPY", 1 if buffers == "pinned-copy" else 0)
+    rl = Relay(host_node, rng0, np.zeros(H, np.uint64), lat, loss, engine=engine)
+    b, st = _edge_round(start, ra, seed=3)
+    chance = (st.draw64 >> np.uint64(11)).astype(np.float64) * 2.0**-53
+    onid = np.zeros(H, np.uint64)
+    o = corc.relay_round(b.src_off, b.send_time, b.dst_host, b.payload, host_node, lat, loss, rng0.copy(), onid,
+                         start + ra, start + 100 * ra, 0, chance=chance)
+    ps = None if buffers == "pageable" else PinnedStages.pinned(engine.lib, st.run_host, st.run_count, st.sends)
+    try:
+        fr = rl.flush(st.run_host, st.run_count, st.sends, start, start + ra, start + 100 * ra, 0, pinned=ps)
+    finally:
+        if ps is not None:
+            ps.free()
+    _check(fr, o, st, np.zeros(H, np.uint64), start + ra)
+
+
+def test_flush_offsets_pass_one_scan_tile(engine):
+    """8193 hosts with about one send each: the grouped offsets' 8194 entries pass one 8192-entry
+    scan tile (scan.h), as d_off's do in tests/test_offers_gpu.py."""
+    from shadow_amd import synth
+    from shadow_amd.relay import PinnedStages, Relay
+    H, NN, P = 8193, 60, 8193
+    lat, loss, host_node, rng0 = _case(H, NN, 33)
+    rl = Relay(host_node, rng0, np.zeros(H, np.uint64), lat, loss, engine=engine)
+    start, ra = 10**9, 10**6
+    b = synth.packet_batch(H, P, start, start + ra, seed=72)
+    st = synth.stage_round(b, 3, start, seed=6)
+    chance = (st.draw64 >> np.uint64(11)).astype(np.float64) * 2.0**-53
+    onid = np.zeros(H, np.uint64)
+    o = corc.relay_round(b.src_off, b.send_time, b.dst_host, b.payload, host_node, lat, loss, rng0.copy(), onid,
+                         start + ra, start + 100 * ra, 0, chance=chance)
+    ps = PinnedStages.pinned(engine.lib, st.run_host, st.run_count, st.sends)
+    try:
+        fr = rl.flush(st.run_host, st.run_count, st.sends, start, start + ra, start + 100 * ra, 0, pinned=ps)
+    finally:
+        ps.free()
+    _check(fr, o, st, np.zeros(H, np.uint64), start + ra)
+
+
+def test_flush_refuses_2_32_sends(engine):
+    """Two stages of 2^31 sends each and no array at all: the totals are refused before any array is
+    read (the "2^32 offers" case of tests/test_offers_gpu.py), and nothing was committed."""
+    from shadow_amd import _native as N
+    from shadow_amd._native import ShdError
+    from shadow_amd.relay import PinnedStages, Relay
+    H, start, ra = len(EDGES), 10**9, 10**6
+    lat, loss, host_node, rng0 = _case(H, 4, 31)
+    rl = Relay(host_node, rng0, np.zeros(H, np.uint64), lat, loss, engine=engine)
+    bad = PinnedStages()
+    bad.stages = [N.Stage(2, None, None, 2**31, None)] * 2
+    bad.array = (N.Stage * 2)(*bad.stages)   # (n stays 0: the outputs are never written)
+    with pytest.raises(ShdError, match="INVALID"):
+        rl.flush(None, None, None, start, start + ra, start + 100 * ra, 0, pinned=bad)
+    b, st = _edge_round(start, ra, seed=4)
+    chance = (st.draw64 >> np.uint64(11)).astype(np.float64) * 2.0**-53
+    o = corc.relay_round(b.src_off, b.send_time, b.dst_host, b.payload, host_node, lat, loss, rng0.copy(),
+                         np.zeros(H, np.uint64), start + ra, start + 100 * ra, 0, chance=chance)
+    fr = rl.flush(st.run_host, st.run_count, st.sends, start, start + ra, start + 100 * ra, 0)
+    _check(fr, o, st, np.zeros(H, np.uint64), start + ra)
+
+
 def test_flush_then_device_draws_round(engine):
     """A flush round (CPU draws) followed by a device-drawn round: ids carry over, the device
     streams start where they were."""
