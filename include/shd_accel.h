@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 10
+#define SHD_ABI_VERSION 11
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -117,7 +117,9 @@ shd_status shd_set_stream(shd_ctx* ctx, void* hip_stream);
  * a context's grids between two calls; shd_set_knob overrides one for this context (value < 0: back
  * to the built-in default), shd_get_knob reads it (-1: the built-in default applies).  `name` is
  * spelled with or without the SHD_ prefix (e.g. "SSSP_SLOTS"); an unknown name is SHD_ERR_INVALID.
- * Relay pipeline knobs (RELAY_FORCE_*, RELAY_NO_LDS_MAP) apply from the next shd_relay_setup. */
+ * Relay pipeline knobs (RELAY_FORCE_*, RELAY_NO_LDS_MAP) apply from the next shd_relay_setup.
+ * UPDATE_REPREPARES is a read-only counter: the shd_routing_update_edges calls of this context that
+ * prepared the graph again in place of patching it (shd_set_knob refuses it). */
 shd_status shd_set_knob(shd_ctx* ctx, const char* name, int64_t value);
 shd_status shd_get_knob(const shd_ctx* ctx, const char* name, int64_t* value);
 
@@ -146,6 +148,36 @@ shd_status shd_routing_prepare(shd_ctx* ctx, const shd_graph* g, const uint32_t*
                                uint32_t n_used, uint32_t mode, shd_error* err);
 shd_status shd_routing_run(shd_ctx* ctx, uint32_t algo, uint32_t row_begin, uint32_t row_end,
                            uint64_t* d_lat_out, float* d_loss_out, shd_error* err);
+
+/*
+ * New weights for n edges of the context's prepared graph (shd_routing_prepare's or
+ * shd_routing_build's), patched into the resident arc arrays: a network whose latencies drift or
+ * whose links degrade or fail (packet_loss 1.0) is rebuilt by shd_routing_run alone, without a new
+ * prepare.  (No reference counterpart: its RoutingInfo is built once, sim_config.rs:424-461.)
+ * edge_index[i] is the edge's position in shd_graph's edge arrays (GML order); topology, used set,
+ * mode and directedness stay as prepared.  Every later shd_routing_run, _run_next_hops,
+ * _run_sharded and lookup after a run equals a fresh prepare of the modified graph bit for bit
+ * (latency, loss bits, next hops, error codes with their node ids, shd_routing_info.arcs and
+ * arcs_kept).
+ *   Validation: the whole call is checked before anything changes; a refused call leaves the
+ *     graph as it was.  SHD_ERR_STATE: no prepared graph.  SHD_ERR_INVALID: a NULL array with
+ *     n > 0, an index >= n_edges, latency 0, loss outside [0, 1] or NaN (shd_routing_prepare's
+ *     rules).  n == 0 is SHD_OK and does nothing.
+ *   Duplicates: an edge named more than once takes its last entry.
+ *   Arcs per edge: an undirected edge changes both of its arcs; a parallel edge only its own; a
+ *     self-loop changes its node's diagonal entry (raw loss bits) if the node is used, and no arc.
+ *   Resident table: not touched.  It stays the old network's until the next run, a relay on it
+ *     keeps working until that run, and shd_routing_mirror follows its usual rule.
+ *   Wide latencies (shortest mode): if some arc is >= 2^32 - 1 ns before the call, or an entry of
+ *     the call is, the graph is prepared again from the context's own copies with the new weights
+ *     (same results, a slower call; shd_get_knob counts such calls as UPDATE_REPREPARES).  Direct
+ *     mode keeps the edges' u64 latencies and always patches in place.
+ *   Cost: the first call after a prepare builds the edge -> arc map (O(n_edges log)); every later
+ *     call is O(n) host work, 16 n bytes of upload and three launches, with one synchronisation.
+ *   Communicator: no collective.  Under a communicator every rank applies the same updates.
+ */
+shd_status shd_routing_update_edges(shd_ctx* ctx, uint64_t n, const uint32_t* edge_index,
+                                    const uint64_t* latency_ns, const float* packet_loss, shd_error* err);
 
 /*
  * shd_routing_run plus next hops (the north star's; the reference keeps none: petgraph's
@@ -217,6 +249,33 @@ shd_status shd_assign_ips(uint32_t n_hosts, const uint32_t* node_gml_id, const u
 shd_status shd_relay_setup(shd_ctx* ctx, uint32_t n_hosts, const uint32_t* host_node,
                            uint32_t n_nodes, const uint64_t* lat, const float* loss,
                            const uint64_t* rng_state, const uint64_t* next_event_id);
+
+/*
+ * A new n_nodes x n_nodes table under a relay that keeps everything else (no reference
+ * counterpart; the pair shd_routing_update_edges + resident shd_routing_run + shd_relay_retable
+ * changes the network between two windows).  lat == loss == NULL: the context's resident table,
+ * which must be a full build with n_nodes columns (else SHD_ERR_STATE); host arrays are copied as
+ * in shd_relay_setup.
+ *   Kept: the host -> node map, the stamp order, both buffers of RNG states and event ids, the
+ *     bound of the event ids, the path packet counters (they go on accumulating), the sharding
+ *     and the knobs read at setup.  Recomputed: the table's width (the pipeline choice) and its
+ *     packed form.
+ *   The call revives a relay that a resident run stopped.  SHD_ERR_STATE: a relay never set up,
+ *     or set up before the context's communicator was created, replaced or (a sharded relay)
+ *     destroyed: its shard and exchange buffers follow the communicator, so shd_relay_setup again.
+ *   SHD_ERR_INVALID: n_nodes differs from the setup's; only one of the two arrays is NULL; or the
+ *     runahead is set up and the new table's smallest latency is 0 (Runahead::new asserts a
+ *     non-zero minimum).  A refused call leaves a running relay running on its old table.
+ *   The table takes effect from the next round.  Queues, ledger, both stages and an open window
+ *     are not touched: the call may come between shd_window_close and the next shd_window_open,
+ *     or between an open and its close.
+ *   Runahead: if it is set up, min_possible becomes the smallest latency of the table the relay
+ *     now uses and the lowest used latency is forgotten (manager.rs:246-251 takes min_possible
+ *     from RoutingInfo; a latency observed on the old network says nothing about the new one).
+ *     The pending relay output's earliest deliver time is kept -- shd_runahead_setup would reset it.
+ *   Communicator: local, no collective; every rank calls it.
+ */
+shd_status shd_relay_retable(shd_ctx* ctx, uint32_t n_nodes, const uint64_t* lat, const float* loss);
 
 typedef struct shd_round {
     uint64_t round_end;      /* Worker::round_end_time */

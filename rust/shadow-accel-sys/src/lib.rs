@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 10;
+pub const SHD_ABI_VERSION: u32 = 11;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -186,6 +186,7 @@ extern "C" {
     pub fn shd_routing_build(ctx: *mut shd_ctx, g: *const shd_graph, used: *const u32, n_used: u32, mode: u32, algo: u32, row_begin: u32, row_end: u32, lat_out: *mut u64, loss_out: *mut f32, err: *mut shd_error) -> shd_status;
     pub fn shd_routing_prepare(ctx: *mut shd_ctx, g: *const shd_graph, used: *const u32, n_used: u32, mode: u32, err: *mut shd_error) -> shd_status;
     pub fn shd_routing_run(ctx: *mut shd_ctx, algo: u32, row_begin: u32, row_end: u32, d_lat_out: *mut u64, d_loss_out: *mut f32, err: *mut shd_error) -> shd_status;
+    pub fn shd_routing_update_edges(ctx: *mut shd_ctx, n: u64, edge_index: *const u32, latency_ns: *const u64, packet_loss: *const f32, err: *mut shd_error) -> shd_status;
     pub fn shd_routing_run_next_hops(ctx: *mut shd_ctx, algo: u32, row_begin: u32, row_end: u32, d_lat_out: *mut u64, d_loss_out: *mut f32, d_next_hop: *mut u32, err: *mut shd_error) -> shd_status;
     pub fn shd_routing_build_device(ctx: *mut shd_ctx, g: *const shd_graph, used: *const u32, n_used: u32, mode: u32, algo: u32, row_begin: u32, row_end: u32, d_lat_out: *mut u64, d_loss_out: *mut f32, err: *mut shd_error) -> shd_status;
     pub fn shd_routing_last_info(ctx: *const shd_ctx, info: *mut shd_routing_info) -> shd_status;
@@ -196,6 +197,7 @@ extern "C" {
     pub fn shd_routing_smallest_latency(ctx: *mut shd_ctx, latency_ns: *mut u64) -> shd_status;
     pub fn shd_assign_ips(n_hosts: u32, node_gml_id: *const u32, ip_in: *const u32, ip_out: *mut u32, used_gml: *mut u32, n_used: *mut u32, host_col: *mut u32, err_host: *mut u32) -> shd_status;
     pub fn shd_relay_setup(ctx: *mut shd_ctx, n_hosts: u32, host_node: *const u32, n_nodes: u32, lat: *const u64, loss: *const f32, rng_state: *const u64, next_event_id: *const u64) -> shd_status;
+    pub fn shd_relay_retable(ctx: *mut shd_ctx, n_nodes: u32, lat: *const u64, loss: *const f32) -> shd_status;
     pub fn shd_relay_round(ctx: *mut shd_ctx, batch: *const shd_batch, round: *const shd_round, out: *mut shd_relay_out) -> shd_status;
     pub fn shd_relay_round_device(ctx: *mut shd_ctx, d_batch: *const shd_batch, round: *const shd_round, d_out: *mut shd_relay_out) -> shd_status;
     pub fn shd_relay_flush(ctx: *mut shd_ctx, stages: *const shd_stage, n_stages: u32, time_base: u64, round: *const shd_round, out: *mut shd_flush_out) -> shd_status;

@@ -47,6 +47,7 @@ EXPORTED = [
     "shd_window_open", "shd_window_close", "shd_ledger_record_sharded",
     "shd_outbound_advance_sockets", "shd_window_close_sockets",
     "shd_offers_group", "shd_window_close_staged", "shd_window_records_host", "shd_window_sent_host",
+    "shd_routing_update_edges", "shd_relay_retable",
 ]
 COMM_ID_BYTES = 128
 
@@ -256,6 +257,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                                           P]),
         "shd_window_records_host": (I32, [P, P, P, P, P, U64, P]),
         "shd_window_sent_host": (I32, [P, P, P, U64, P, P, P, U64, P, P]),
+        "shd_routing_update_edges": (I32, [P, U64, P, P, P, P]),
+        "shd_relay_retable": (I32, [P, U32, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 # (the slowest units first, so the parallel build starts them first)
 SRC = [os.path.join(HERE, "csrc", f) for f in ("routing_sssp_lds.hip", "relay_stamp.hip", "relay_bins.hip",
                                                 "routing_sssp_global.hip", "routing_prune.hip",
-                                                "routing.hip", "relay_shard.hip", "routing_wide.hip",
+                                                "routing.hip", "relay_shard.hip", "routing_wide.hip", "routing_update.hip",
                                                 "blocked.hip", "relay_radix.hip", "relay_wide.hip", "relay.hip",
                                                 "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue_pass.hip", "equeue.hip",

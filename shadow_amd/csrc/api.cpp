@@ -412,7 +412,7 @@ shd_status shd_routing_run_sharded(shd_ctx* ctx, uint32_t algo, uint64_t* d_lat_
 shd_status shd_set_knob(shd_ctx* ctx, const char* name, int64_t value) {
     if (!ctx) return SHD_ERR_INVALID;
     const int k = Knobs::find(name);
-    if (k < 0) return SHD_ERR_INVALID;
+    if (k < 0 || k == K_UPDATE_REPREPARES) return SHD_ERR_INVALID;   // (a counter: read only)
     ctx->knobs.v[k] = value < 0 ? -1 : value;
     ctx->stats_on = ctx->knobs.on(K_SSSP_STATS);
     ctx->spin_wait = ctx->knobs.get(K_SPIN_WAIT, 1) != 0;
@@ -423,7 +423,7 @@ shd_status shd_get_knob(const shd_ctx* ctx, const char* name, int64_t* value) {
     if (!ctx || !value) return SHD_ERR_INVALID;
     const int k = Knobs::find(name);
     if (k < 0) return SHD_ERR_INVALID;
-    *value = ctx->knobs.v[k];
+    *value = k == K_UPDATE_REPREPARES ? (int64_t)ctx->upd_reprepares : ctx->knobs.v[k];
     return SHD_OK;
 }
 

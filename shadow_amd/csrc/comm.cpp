@@ -388,7 +388,7 @@ shd_status shd_comm_init(shd_ctx* ctx, int32_t n_ranks, int32_t rank, const uint
     c->rank = rank;
     c->size = n_ranks;
     ctx->comm = std::move(c);
-    ctx->relay.ready = false;   // the relay's source shard follows the communicator: set up again
+    ctx->relay.ready = ctx->relay.set_up = false;   // the relay's source shard follows the communicator: set up again
     ctx->eq.ready = false;      // so do the queues' destination shard
     return SHD_OK;
 }
@@ -425,7 +425,7 @@ shd_status shd_comm_init_local(shd_ctx** ctxs, int32_t n_ranks) {
         c->rank = r;
         c->size = n_ranks;
         ctxs[r]->comm = std::move(c);
-        ctxs[r]->relay.ready = false;
+        ctxs[r]->relay.ready = ctxs[r]->relay.set_up = false;
         ctxs[r]->eq.ready = false;
     }
     return SHD_OK;
@@ -447,7 +447,7 @@ shd_status shd_comm_init_host(shd_ctx* ctx, int32_t n_ranks, int32_t rank, const
         return SHD_ERR_NOMEM;
     }
     ctx->comm = std::move(c);
-    ctx->relay.ready = false;
+    ctx->relay.ready = ctx->relay.set_up = false;
     ctx->eq.ready = false;
     return SHD_OK;
 }
@@ -463,7 +463,7 @@ shd_status shd_comm_destroy(shd_ctx* ctx) {
     if (!ctx) return SHD_ERR_INVALID;
     SHD_HIP(hipSetDevice(ctx->device));
     if (ctx->stream) SHD_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->comm && ctx->relay.sharded) ctx->relay.ready = false;
+    if (ctx->comm && ctx->relay.sharded) ctx->relay.ready = ctx->relay.set_up = false;
     if (ctx->comm && ctx->comm->size > 1) ctx->eq.ready = false;
     ctx->comm.reset();
     return SHD_OK;

@@ -5,6 +5,7 @@
 
 #include "comm.h"
 #include "common.h"
+#include "edge_update.h"
 #include "knobs.h"
 #include "ledger_book.h"
 
@@ -242,6 +243,9 @@ struct WindowState {
 
 struct RelayState {
     bool ready = false;
+    // shd_relay_setup has succeeded under the present communicator: shd_relay_retable may revive
+    // the relay after a resident run stopped it (a change of communicator clears both flags)
+    bool set_up = false;
     uint32_t n_hosts = 0;
     // source hosts this context stamps: all hosts, or (set up under a communicator of > 1
     // ranks) the rank's shard [src_lo, src_lo + n_src), which is also its destination shard
@@ -317,6 +321,11 @@ struct PreparedGraph {
     std::vector<uint32_t> used, node_ids, es, ed;
     std::vector<uint64_t> el;
     std::vector<float> ep;
+    // shd_routing_update_edges (routing_update.hip): the two relabellings (node -> new id) that
+    // prepare made, and the edge -> arc-slot map, built at the first update of a prepared graph
+    std::vector<uint32_t> pi_r, pi_s;
+    EdgeSlots upd;
+    std::vector<int32_t> upd_col;   // node -> used index (-1: unused), with the map
     shd_graph view() const {
         shd_graph g{};
         g.n_nodes = V;
@@ -335,7 +344,8 @@ struct PreparedGraph {
 
 struct shd_ctx;
 namespace shd {
-// h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [32, 36) flush checks, [36, 38) offer-group checks,
+// h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [16, 18) the edge update's min / max arc latency,
+// [32, 36) flush checks, [36, 38) offer-group checks,
 // [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker;
 // [81, 86) outbound-stage words
 constexpr int kPinWords = 88;
@@ -397,7 +407,12 @@ struct shd_ctx {
     shd::DevBuf g_off, g_dst, g_lat, g_q, g_lat64, g_used, g_diag_lat, g_diag_loss, g_flags,
         g_dense, g_prune_dst, g_prune_dst2, g_prune_cnt, g_prune_nn, g_labels, g_aux, g_arc16, g_arc8, g_aq, g_fw, g_glab, g_pred,
         g_offr, g_usedr, g_arc8r, g_aqr,   // locality-ordered copies (global-label kernel)
-        g_offs, g_useds, g_arc16s;         // wave-spread copies (1024-thread LDS kernel)
+        g_offs, g_useds, g_arc16s,         // wave-spread copies (1024-thread LDS kernel)
+        g_umap, g_umap_r, g_umap_s,        // shd_routing_update_edges: per edge the two arc slots (main, copies)
+        g_urec, g_ured;                    // its records, and the min / max arc latency words
+    shd::DevBuf g_red;                     // min_u64_device / max_u64_device's result word
+    // update calls that prepared the graph again (a wide graph); shd_get_knob reads it as UPDATE_REPREPARES
+    uint64_t upd_reprepares = 0;
     uint32_t* nh_out = nullptr;   // next-hop rows of the running build (shd_routing_run_next_hops)
     // global-label slots left unlaunched while a sharded build's previous chunk is still being
     // exchanged on the side stream: the persistent kernel fills every CU's LDS, so RCCL's

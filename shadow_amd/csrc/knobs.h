@@ -4,7 +4,10 @@
 // grids between two builds; shd_set_knob / shd_get_knob (api.cpp) change or inspect them per
 // context afterwards.  TEST_FAIL is fault injection for the failure-agreement tests (1: a sharded
 // relay round fails on this rank after its sizing summary is read; 3: the host transport's staging
-// cannot be allocated): only shd_set_knob sets it, the environment never does.
+// cannot be allocated): only shd_set_knob sets it, the environment never does.  UPDATE_REPREPARES
+// is a counter, not a setting: shd_get_knob returns how many shd_routing_update_edges calls of the
+// context prepared its graph again in place of patching it (a graph with an arc beyond u32), which
+// results cannot show; neither shd_set_knob nor the environment sets it.
 #pragma once
 #include <stdint.h>
 
@@ -20,7 +23,7 @@ namespace shd {
     X(EQ_SEARCH_ONLY) X(EQ_MAX_RUNS) X(RELAY_GROUP_SENDS) X(HIST_SCALAR) X(RELAY_FORCE_V1)      \
     X(RELAY_FORCE_V3) X(RELAY_NO_LDS_MAP) X(SHARD_CHUNK_ROWS) X(SHARD_REPLICATE_MB)             \
     X(SHARD_RESERVE_SLOTS) X(RELAY_SHARD_X24) X(FLUSH_COPY) X(PRUNE_SHAPE) X(RELAY_SCAN2)       \
-    X(LEDGER_REMAP_SEARCH) X(PRUNE_FUSED) X(TEST_FAIL)
+    X(LEDGER_REMAP_SEARCH) X(PRUNE_FUSED) X(TEST_FAIL) X(UPDATE_REPREPARES)
 
 enum Knob : int {
 #define SHD_KNOB_ENUM(n) K_##n,
@@ -53,7 +56,7 @@ struct Knobs {
             char var[64] = "SHD_";
             std::strncat(var, name(k), sizeof(var) - 5);
             const char* s = std::getenv(var);
-            v[k] = k != K_TEST_FAIL && s && *s ? (int64_t)std::strtoull(s, nullptr, 10) : -1;
+            v[k] = k != K_TEST_FAIL && k != K_UPDATE_REPREPARES && s && *s ? (int64_t)std::strtoull(s, nullptr, 10) : -1;
         }
     }
     uint32_t get(Knob k, uint32_t dflt) const { return v[k] < 0 ? dflt : (uint32_t)v[k]; }

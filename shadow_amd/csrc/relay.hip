@@ -259,6 +259,58 @@ shd_status shd_relay_setup(shd_ctx* ctx, uint32_t n_hosts, const uint32_t* host_
         }
     }
     R.ready = true;
+    R.set_up = true;
+    return SHD_OK;
+}
+
+// A new table under a relay that keeps everything else: the host -> node map, the stamp order,
+// the hosts' RNG streams and event ids, seq_bound, the path counters, the sharding and the knobs
+// read at setup.  Everything is checked (and the table's extremes are known) before anything changes.
+shd_status shd_relay_retable(shd_ctx* ctx, uint32_t n_nodes, const uint64_t* lat, const float* loss) {
+    if (!ctx) return SHD_ERR_INVALID;
+    RelayState& R = ctx->relay;
+    if (!R.set_up) return SHD_ERR_STATE;
+    if (n_nodes != R.n_nodes || (lat == nullptr) != (loss == nullptr)) return SHD_ERR_INVALID;
+    SHD_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const uint64_t nn = (uint64_t)n_nodes * n_nodes;
+    RoundState& W = ctx->rnd;
+    uint64_t mx = 0, mn = ~0ull;
+    if (!lat) {
+        if (!ctx->t_full || ctx->t_cols != n_nodes) return SHD_ERR_STATE;
+        SHD_TRY(max_u64_device(ctx, ctx->t_lat.as<uint64_t>(), nn, &mx));
+        if (W.ready) SHD_TRY(min_u64_device(ctx, ctx->t_lat.as<uint64_t>(), nn, &mn));
+    } else {
+        for (uint64_t i = 0; i < nn; ++i) {
+            mx = std::max(mx, lat[i]);
+            mn = std::min(mn, lat[i]);
+        }
+    }
+    if (W.ready && mn == 0) return SHD_ERR_INVALID;   // Runahead::new asserts a non-zero minimum latency
+    if ((mx >> 32) == 0) SHD_TRY(R.path.ensure(nn * 8));
+    if (lat) {
+        SHD_TRY(R.lat.ensure(nn * 8));
+        SHD_TRY(R.loss.ensure(nn * 4));
+        SHD_HIP(hipMemcpyAsync(R.lat.p, lat, nn * 8, hipMemcpyHostToDevice, s));
+        SHD_HIP(hipMemcpyAsync(R.loss.p, loss, nn * 4, hipMemcpyHostToDevice, s));
+    }
+    R.own_table = lat != nullptr;
+    R.table_narrow = (mx >> 32) == 0;
+    if (R.table_narrow) {
+        const uint64_t* tl = R.own_table ? R.lat.as<uint64_t>() : ctx->t_lat.as<uint64_t>();
+        const float* tp = R.own_table ? R.loss.as<float>() : ctx->t_loss.as<float>();
+        pack_path<<<div_up(nn, 256), 256, 0, s>>>(tl, tp, nn, R.path.as<uint2>());
+        SHD_HIP(hipGetLastError());
+    }
+    SHD_HIP(hipStreamSynchronize(s));   // the caller's arrays are free again
+    R.ready = true;
+    if (W.ready) {
+        // manager.rs:246-251 takes min_possible from RoutingInfo; a latency observed on the old
+        // network says nothing about the new one.  batch_min_deliver stays: the pending relay
+        // output is still to be merged (the reason this call exists beside shd_runahead_setup)
+        W.min_possible = mn;
+        W.min_used = ~0ull;
+    }
     return SHD_OK;
 }
 

@@ -60,12 +60,13 @@ __global__ void min_u64_kernel(const uint64_t* __restrict__ d, uint64_t n,
 
 template <bool MAX>
 static shd_status minmax_u64_device(shd_ctx* ctx, const uint64_t* d, uint64_t n, uint64_t* out) {
-    SHD_TRY(ctx->g_aux.ensure(8));
-    SHD_HIP(hipMemsetAsync(ctx->g_aux.p, MAX ? 0 : 0xFF, 8, ctx->stream));
+    // (a word of its own: g_aux holds the prepared graph's arc losses, which the next build reads)
+    SHD_TRY(ctx->g_red.ensure(8));
+    SHD_HIP(hipMemsetAsync(ctx->g_red.p, MAX ? 0 : 0xFF, 8, ctx->stream));
     const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
     (MAX ? max_u64_kernel : min_u64_kernel)<<<grid ? grid : 1, 256, 0, ctx->stream>>>(
-        d, n, reinterpret_cast<unsigned long long*>(ctx->g_aux.p));
-    SHD_HIP(hipMemcpyAsync(out, ctx->g_aux.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        d, n, reinterpret_cast<unsigned long long*>(ctx->g_red.p));
+    SHD_HIP(hipMemcpyAsync(out, ctx->g_red.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     SHD_HIP(hipStreamSynchronize(ctx->stream));
     return SHD_OK;
 }

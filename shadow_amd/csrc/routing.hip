@@ -260,6 +260,7 @@ static shd_status prepare_reordered(shd_ctx* ctx, const HostGraph& H, const uint
                                                    ctx->g_arc8r.as<uint2>(), ctx->g_aqr.as<float>(), A);
     SHD_HIP(hipGetLastError());
     SHD_HIP(hipStreamSynchronize(s));   // the temporaries are freed on return
+    P.pi_r = std::move(pi);   // shd_routing_update_edges finds the copy's slots through it
     P.reordered = true;
     return SHD_OK;
 }
@@ -333,6 +334,7 @@ static shd_status prepare_spread(shd_ctx* ctx, const HostGraph& H, const uint32_
                                                   ctx->g_arc16s.as<uint4>(), d_a8.as<uint2>(), d_q.as<float>(), A);
     SHD_HIP(hipGetLastError());
     SHD_HIP(hipStreamSynchronize(s));   // the temporaries are freed on return
+    P.pi_s = std::move(pi);   // (as P.pi_r)
     P.spread = true;
     return SHD_OK;
 }
@@ -342,6 +344,7 @@ shd_status routing_prepare_impl(shd_ctx* ctx, const shd_graph* g, const uint32_t
     if (err) *err = shd_error{SHD_OK, 0, 0};
     PreparedGraph& P = ctx->prep;
     P.ready = false;
+    P.upd.built = false;   // the edge -> arc-slot map of the graph before (shd_routing_update_edges)
     SHD_TRY(validate(g, used, n_used));
     if (mode != SHD_ROUTE_SHORTEST && mode != SHD_ROUTE_DIRECT) return SHD_ERR_INVALID;
     hipStream_t s = ctx->stream;

@@ -33,6 +33,19 @@
 //                           relaxations), included by the two SSSP units
 //   routing_prune.hip       dense_build, prune_rows, prune_rows2, nearest_rows, prune_fused
 //   routing_wide.hip        sssp_wide_round, wide_*, arcs_q, direct_*
+//   routing_update.hip      edge_patch, edge_patch_direct, lat_minmax: shd_routing_update_edges
+// Edge updates (shd_routing_update_edges): the builds recompute everything but the prepared
+// graph's own arrays on every run, so new weights for n edges are one patch of those arrays.  The
+// host (edge_update.h, no HIP types) validates the whole call, keeps the last entry of an edge
+// named twice, and maps an edge to its arc slots in build_csr's order (the map is built at the
+// first update after a prepare and is resident on the device, as are the slots in the two
+// relabelled copies, found through the node permutations prepare keeps).  edge_patch writes whole
+// records into g_lat / g_aux / g_arc16 / g_arc8 / g_aq, the copies and the diagonal; lat_minmax
+// then reduces the arc latencies so that PreparedGraph's max / min are exact (the prune's bin
+// shift, the padded kernels' overflow guard, the bucket widths); the mean keeps prepare's
+// definition through an integer sum adjusted per edge; the kept-arc counts are counted again by
+// the next build.  A graph with an arc beyond u32 before or after the call is prepared again from
+// the context's host copies.
 #pragma once
 #include <algorithm>
 #include <vector>

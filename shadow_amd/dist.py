@@ -148,6 +148,12 @@ class ShardedRelay:
                                            N.ptr(loss), N.ptr(np.ascontiguousarray(rng_state, np.uint64)),
                                            N.ptr(np.ascontiguousarray(next_event_id, np.uint64))),
                 "shd_relay_setup")
+        self.n_nodes = lat.shape[0]
+
+    def retable(self, lat=None, loss=None):
+        """``shd_relay_retable``: as ``Relay.retable``; local, every rank calls it."""
+        from .relay import retable
+        retable(self.eng, self.n_nodes, lat, loss)
 
     def round_device(self, d_off, d_time, d_dst, d_pay, round_, d_status) -> N.RelayOut:
         n = int(d_time.numel())

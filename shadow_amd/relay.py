@@ -108,6 +108,16 @@ def group_by_source(n_hosts: int, src_host: np.ndarray):
     return order, off
 
 
+def retable(eng: Engine, n_nodes: int, lat=None, loss=None):
+    """``shd_relay_retable`` on an engine's relay: a new n_nodes x n_nodes table (host arrays, or
+    None for the engine's resident table); everything else of the relay is kept."""
+    if lat is not None:
+        lat = np.ascontiguousarray(lat, np.uint64)
+    if loss is not None:
+        loss = np.ascontiguousarray(loss, np.float32)
+    N.check(eng.lib.shd_relay_retable(eng.ctx, n_nodes, N.ptr(lat), N.ptr(loss)), "shd_relay_retable")
+
+
 class Relay:
     """Device-resident relay tables of one GPU (``shd_relay_setup``)."""
 
@@ -128,6 +138,13 @@ class Relay:
         N.check(self.eng.lib.shd_relay_setup(self.eng.ctx, self.n_hosts, N.ptr(self.host_node),
                                              n_nodes, N.ptr(lat), N.ptr(loss), N.ptr(rng),
                                              N.ptr(nid)), "shd_relay_setup")
+
+    def retable(self, lat=None, loss=None):
+        """``shd_relay_retable``: the relay takes a new table (None: the engine's resident table,
+        which revives a relay that a resident routing run stopped) and keeps its host map, RNG
+        streams, event ids and path counters.  With the runahead set up, its minimum possible
+        latency becomes the new table's smallest."""
+        retable(self.eng, self.n_nodes, lat, loss)
 
     def round(self, src_off, send_time, dst_host, payload, round_end: int, sim_end: int,
               bootstrap_end: int = 0, chance=None) -> RoundResult:

@@ -237,6 +237,17 @@ class NetworkGraph:
         t = PathTable(self, list(used), lat.cpu().numpy().view(np.uint64), loss.cpu().numpy(), rb)
         return t, nh.cpu().numpy().view(np.uint32)
 
+    def prepare(self, nodes, engine: Engine | None = None, mode: int = N.ROUTE_SHORTEST) -> "PreparedGraph":
+        """``shd_routing_prepare``: the graph resident on the engine, for builds that repeat while
+        edge weights change (``PreparedGraph.update_edges`` / ``run``)."""
+        eng = engine or default_engine()
+        used = np.ascontiguousarray(nodes, np.uint32)
+        err = N.Error()
+        g = self._cgraph()
+        st = eng.lib.shd_routing_prepare(eng.ctx, C.byref(g), N.ptr(used), len(used), mode, C.byref(err))
+        self._raise(st, err)
+        return PreparedGraph(self, used, eng)
+
     @staticmethod
     def _raise(st, err):
         if st in (1, 2):
@@ -246,6 +257,62 @@ class NetworkGraph:
             raise RoutingPanic(f"assertion failed: paths.len() == nodes.len().pow(2) "
                                f"(no path from node {err.node_a} to {err.node_b})")
         N.check(st, "routing", err)
+
+
+class PreparedGraph:
+    """The engine's prepared graph (``NetworkGraph.prepare``).  The reference builds its
+    ``RoutingInfo`` once (sim_config.rs:424-461); here the edge weights may change between builds:
+    ``update_edges`` patches the resident arcs, ``run`` rebuilds the table from them.  A new
+    prepare or build on the same engine replaces the prepared graph."""
+
+    def __init__(self, graph: NetworkGraph, used: np.ndarray, engine: Engine):
+        self.graph, self.used, self.eng = graph, used, engine
+        # the weights the engine holds now (the graph's own arrays are left alone)
+        self.edge_latency_ns = graph.edge_latency_ns.copy()
+        self.edge_packet_loss = graph.edge_packet_loss.copy()
+
+    def update_edges(self, edge_index, latency_ns, packet_loss):
+        """``shd_routing_update_edges``: new weights for the named edges (positions in the graph's
+        edge arrays; an edge named more than once takes its last entry).  ``edge_latency_ns`` and
+        ``edge_packet_loss`` of this handle follow: they are the network the next ``run`` builds."""
+        idx = np.ascontiguousarray(edge_index, np.uint32)
+        lat = np.ascontiguousarray(latency_ns, np.uint64)
+        loss = np.ascontiguousarray(packet_loss, np.float32)
+        if not (idx.shape == lat.shape == loss.shape and idx.ndim == 1):
+            raise ValueError("edge_index, latency_ns and packet_loss must be 1-d arrays of one length")
+        err = N.Error()
+        st = self.eng.lib.shd_routing_update_edges(self.eng.ctx, len(idx), N.ptr(idx), N.ptr(lat), N.ptr(loss),
+                                                   C.byref(err))
+        NetworkGraph._raise(st, err)
+        self.edge_latency_ns[idx] = lat     # (numpy keeps the last of repeated indices)
+        self.edge_packet_loss[idx] = loss
+
+    def run(self, algo: int = N.ALGO_AUTO, rows=None, next_hops: bool = False):
+        """``shd_routing_run`` (``shd_routing_run_next_hops``) into fresh device buffers: the
+        PathTable of rows [rows[0], rows[1]) (all rows when None), and the next hops when asked."""
+        import torch
+        n = len(self.used)
+        rb, re = (0, n) if rows is None else rows
+        lat = torch.empty((re - rb, n), dtype=torch.int64, device="cuda")
+        loss = torch.empty((re - rb, n), dtype=torch.float32, device="cuda")
+        nh = torch.empty((re - rb, n), dtype=torch.int32, device="cuda") if next_hops else None
+        torch.cuda.synchronize()
+        err = N.Error()
+        lib, ctx = self.eng.lib, self.eng.ctx
+        if next_hops:
+            st = lib.shd_routing_run_next_hops(ctx, algo, rb, re, N.ptr(lat), N.ptr(loss), N.ptr(nh), C.byref(err))
+        else:
+            st = lib.shd_routing_run(ctx, algo, rb, re, N.ptr(lat), N.ptr(loss), C.byref(err))
+        NetworkGraph._raise(st, err)
+        t = PathTable(self.graph, list(self.used), lat.cpu().numpy().view(np.uint64), loss.cpu().numpy(), rb)
+        return (t, nh.cpu().numpy().view(np.uint32)) if next_hops else t
+
+    def run_resident(self, algo: int = N.ALGO_AUTO):
+        """``shd_routing_run`` of every row into the engine's resident table (what lookups and a
+        relay on the resident table read; ``Relay.retable()`` adopts it)."""
+        err = N.Error()
+        st = self.eng.lib.shd_routing_run(self.eng.ctx, algo, 0, 0, None, None, C.byref(err))
+        NetworkGraph._raise(st, err)
 
 
 class RoutingInfo:
