@@ -113,7 +113,14 @@ __device__ __forceinline__ void relax_node_pad(uint32_t u, uint32_t gl, uint64_t
     static_assert(G * R == 32 || G * R == 64, "a padded list holds whole G x R steps");
     const uint64_t ku = lab[u];
     const uint32_t lu = key_lat(ku);
-    if (lu > lat_guard) ovf = true;
+    // the build is flagged and this node's arcs are left alone: their unchecked sums could wrap to
+    // labels below every real one, each of which wraps on in turn -- the labels then sink a few
+    // ns per sweep and these sweeps have no cap (arcs in [2^31, 2^32 - 3] on 33 nodes: more than
+    // 200,000 sweeps).  The table is the wide rerun's either way
+    if (lu > lat_guard) {
+        ovf = true;
+        return;
+    }
     const float qu = one_minus(key_loss(ku));
     const uint2 r = CACHE ? rng[u] : make_uint2(abeg[u], aend[u]);
     for (uint32_t k0 = r.x; k0 < r.y; k0 += G * R) {

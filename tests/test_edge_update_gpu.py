@@ -397,3 +397,58 @@ def test_sharded_run_equals_the_one_context_table(fresh):
     finally:
         for e in engines:
             e.close()
+
+
+@pytest.mark.parametrize("which", ["edge01", "rung23"])
+def test_ladder_edge_across_the_u32_seam(engine, fresh, which):
+    """One edge of the ladder (tests/seam_graphs.py; largest distance 2^32 - 2) to 2^32 - 2, the
+    last latency a packed arc holds: patched in place, and the largest arc now switches the padded
+    kernels' guard off.  To 2^32 - 1, the narrow labels' sentinel: prepared again, on the u64
+    arcs.  Back to 1 ns: prepared again, packed.  Edge (0, 1) carries every long path (the table
+    goes past 2^33); the rung (2, 3) drops out of every shortest path, only the arc maximum moves."""
+    from tests import seam_graphs as SG
+    ids, s, d, l, p, directed = SG.ladder(2**32 - 2, False)
+    edge, ends = {"edge01": (SG.LADDER_E01, (0, 1)), "rung23": (SG.LADDER_E23, (2, 3))}[which]
+    assert (int(s[edge]), int(d[edge])) == ends
+    net = Net(ids, s, d, l, p, directed, np.arange(8))
+    pg = net.graph().prepare(net.used, engine)
+    again = engine.get_knob("UPDATE_REPREPARES")
+    for lat_e, more in ((2**32 - 2, 0), (2**32 - 1, 1), (1, 1)):
+        pg.update_edges([edge], [lat_e], [0.07])
+        again += more
+        assert engine.get_knob("UPDATE_REPREPARES") == again, lat_e
+        assert int(pg.edge_latency_ns[s != d].max()) == (lat_e if lat_e > 1 else 2**31 - 4 if edge == 0 else 2**31)
+        code, lat, loss, _ = corc.routing(8, s, d, pg.edge_latency_ns, pg.edge_packet_loss, directed, net.used)
+        assert code == "OK"
+        for algo in (0, 4):
+            same_as_fresh(engine, fresh, net, pg, algo, lat, loss.view(np.uint32))
+            if int(lat[~np.eye(8, dtype=bool)].max()) >= 2**32 - 1:
+                assert engine.last_info()["wide_latency"] == 1
+
+
+def test_patch_keeps_the_largest_arc_at_the_last_narrow_latency(engine, fresh):
+    """huge_complete(65): arcs in [2^31, 2^32 - 2] with the largest exactly 2^32 - 2 (guard off:
+    the unpadded kernel on the padded lists).  Patches move that largest arc to another edge and
+    rewrite a quarter of the others inside the range: lat_minmax must leave max_arc_lat at
+    2^32 - 2, and every build equals a fresh prepare's."""
+    from tests import seam_graphs as SG
+    ids, s, d, l, p, directed = SG.huge_complete(65, 2**32 - 2, 65)
+    net = Net(ids, s, d, l, p, directed, np.arange(65))
+    arcs = np.flatnonzero(s != d)
+    top = int(arcs[np.argmax(l[arcs])])
+    other = int(arcs[0] if arcs[0] != top else arcs[1])
+    rng = np.random.default_rng(65)
+    some = rng.choice(arcs[(arcs != top) & (arcs != other)], len(arcs) // 4, replace=False)
+    steps = [([top, other], [2**31, 2**32 - 2], [0.1, 0.2]),
+             (some, rng.integers(2**31, 2**32 - 2, len(some), dtype=np.uint64), rng.uniform(0, 0.3, len(some))),
+             ([other, top], [2**32 - 3, 2**32 - 2], [0.2, 0.0])]
+    pg = net.graph().prepare(net.used, engine)
+    again = engine.get_knob("UPDATE_REPREPARES")
+    for idx, nl, np_ in steps:
+        pg.update_edges(np.asarray(idx, np.uint32), np.asarray(nl, np.uint64), np.asarray(np_, np.float32))
+        assert int(pg.edge_latency_ns[arcs].max()) == 2**32 - 2
+        code, lat, loss, _ = corc.routing(65, s, d, pg.edge_latency_ns, pg.edge_packet_loss, directed, net.used)
+        assert code == "OK"
+        for algo in (0, 2, 4):
+            same_as_fresh(engine, fresh, net, pg, algo, lat, loss.view(np.uint32))
+    assert engine.get_knob("UPDATE_REPREPARES") == again

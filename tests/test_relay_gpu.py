@@ -470,3 +470,42 @@ def test_test_fail_is_not_read_from_the_environment():
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("knobs ")]
     assert lines == ["knobs None 1"], p.stdout[-2000:]
+
+
+@pytest.mark.parametrize("top,pipes", [(2**32 - 1, (7, 3)), (2**32, (1,))], ids=["top_is_u32_max", "top_is_2^32"])
+def test_engine_built_table_at_the_u32_seam(engine, top, pipes):
+    """The routing build hands its table to the relay across the seam: routing's narrow labels
+    stop at 2^32 - 2 (2^32 - 1 is their sentinel), the relay's narrow table holds any u32, 2^32 - 1
+    included (no sentinel there).  The engine-built ladder tables (tests/seam_graphs.py) whose
+    largest entry is 2^32 - 1 (narrow pipeline) and 2^32 (64-bit pipeline), 64 hosts on the eight
+    nodes, one round of 2,000 sends: statuses and every event field against the C restatement."""
+    from shadow_amd import synth
+    from shadow_amd.relay import Relay
+    from shadow_amd.routing import NetworkGraph
+    from tests import seam_graphs as SG
+    gr = SG.ladder(top, False)
+    used = np.arange(8, dtype=np.uint32)
+    code, lat, loss, _ = corc.routing(8, gr[1], gr[2], gr[3], gr[4], gr[5], used)
+    assert code == "OK" and int(lat.max()) == top
+    t = NetworkGraph(*gr).compute_shortest_paths(used, engine)
+    assert np.array_equal(t.lat, lat) and np.array_equal(t.loss.view(np.uint32), loss.view(np.uint32))
+    H = 64
+    start, ra = 10**9, 10**6
+    b = synth.packet_batch(H, 2000, start, start + ra, seed=21)
+    host_node = synth.c5_host_nodes(H, 8)
+    rng0 = synth.host_rng_states(H, 1)
+    src = np.repeat(np.arange(H), np.diff(b.src_off))
+    seam = lat[host_node[src], host_node[b.dst_host]] == top
+    assert seam.sum() > 20     # sends between hosts of node 0 and of the top node, both ways
+    o = corc.relay_round(b.src_off, b.send_time, b.dst_host, b.payload, host_node, lat, loss, rng0.copy(),
+                         np.zeros(H, np.uint64), start + ra, 10**13, 0)
+    assert (o["status"][seam] == 2).any()
+    rl = Relay(host_node, rng0, np.zeros(H, np.uint64), t.lat, t.loss, engine=engine)
+    r = rl.round(b.src_off, b.send_time, b.dst_host, b.payload, start + ra, 10**13, 0)
+    assert rl.last_pipeline() in pipes
+    assert np.array_equal(r.status, o["status"])
+    ev = o["events"]
+    assert np.array_equal(r.ev_off, ev["off"])
+    for k in ("deliver", "src", "seq", "pkt"):
+        assert np.array_equal(getattr(r, "ev_" + k), ev[k]), k
+    assert (r.min_deliver, r.min_latency, r.n_sent) == (o["min_deliver"], o["min_latency"], o["n_sent"])
