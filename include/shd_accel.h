@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define SHD_ABI_VERSION 11
+#define SHD_ABI_VERSION 12
 
 typedef enum shd_status {
     SHD_OK = 0,
@@ -1150,6 +1150,69 @@ shd_status shd_window_records_host(shd_ctx* ctx, uint32_t* off, uint32_t* pkt, u
 shd_status shd_window_sent_host(shd_ctx* ctx, uint32_t* sent_pkt, uint8_t* sent_status, uint64_t cap_batch,
                                 uint32_t* loc_off, uint32_t* loc_pkt, uint64_t* loc_time, uint64_t cap_local,
                                 uint64_t* n_batch, uint64_t* n_local);
+
+/* ---------------------------------------------------------------------------------------
+ * Bandwidth changes on running stages: re-rate the token buckets (ABI 12).  Link capacity is a
+ * host's bw_down / bw_up (relay/mod.rs:277-302 builds both relays' buckets from it, once); the
+ * setup calls are the only other way to another rate, and they start the stage over.  These
+ * calls change the named hosts' buckets and nothing else: queued packets, CoDel state, the cached
+ * packet, the outstanding forward task and the sockets stay as they are.
+ *
+ * The reference has no counterpart; a re-rate of one bucket at emulated time `at_time` to
+ * (capacity C, increment I, interval N) is put together from its pieces (token_bucket.rs:37-60,
+ * :127-157):
+ *   bucket -> bucket     lazy_refill(at_time) under the old parameters -- the old rate holds up to
+ *                        at_time -- then new_inner(C, I, N, at_time) whose balance is
+ *                        min(refilled balance, C) instead of C.  The new refill grid starts at at_time.
+ *   none -> bucket       (none: all three parameters 0) new_inner(C, I, N, at_time), full
+ *   bucket -> none       the host is unlimited; last_refill reads back as at_time, the rest as 0
+ *   none -> none         nothing changes
+ * An outstanding forward task keeps its time (the reference cannot cancel a scheduled task); a
+ * cached packet stays cached and is weighed against the new bucket when its task runs.  Some but
+ * not all of C, I, N zero is refused, as at setup.  A host named more than once takes its last
+ * entry.  n == 0 is SHD_OK and does nothing.  All arrays are host arrays; `host` is the stage's
+ * own index (a sharded rank's local one, global id first_host + host).  No collective: each rank
+ * re-rates its own hosts.
+ *
+ * A call is refused whole -- nothing changed on the device or the host:
+ *   SHD_ERR_STATE    the stage is not ready: before its setup, and after a contract error until
+ *                    the next setup (where the advance returns it)
+ *   SHD_ERR_INVALID  before any launch: a NULL array with n > 0; an index >= the stage's hosts;
+ *                    some-but-not-all-zero parameters; at_time below the stage's previous window_end
+ *   SHD_ERR_INVALID  on the device, for any named host, the lowest such index in *err_host (may be
+ *                    NULL; untouched otherwise): at_time before the bucket's last_refill (the
+ *                    reference's duration_since would panic); a refill to at_time where the
+ *                    reference panics (as the advance's); an outstanding forward task earlier than
+ *                    at_time (it would run before the new bucket's last_refill); a capacity C > 0
+ *                    below the total size of a packet the host stores now, the cached one
+ *                    included -- a blocked packet's task must be able to forward it.  An outbound
+ *                    packet whose dst is the host itself never meets the bucket and is exempt.
+ * After a successful call an event or offer of a re-rated host earlier than at_time is the caller's
+ * contract violation: it meets the advance's "a time before the bucket's last refill".
+ *
+ *   shd_tb_update                 the replay engine's buckets (shd_tb_setup).  A Pending relay stays
+ *                                 Pending until its deadline; only the time rules apply.
+ *   shd_inbound_update_buckets    the inbound stage's (bw_down)
+ *   shd_outbound_update_buckets   the outbound stage's (bw_up), under any discipline
+ *   shd_window_update_bandwidth   both stages from rates in bytes per second, each direction by
+ *                                 create_token_bucket (relay/mod.rs:291-302: increment =
+ *                                 max(1, rate / 1000), capacity = increment + 1500, interval 1 ms);
+ *                                 UINT64_MAX leaves that direction as it is.  Only between a close
+ *                                 and the next open: SHD_ERR_STATE while a window is open or before
+ *                                 the window's parts are set up.  Both stages are checked before
+ *                                 either changes, so a refusal by one leaves both untouched.
+ * ------------------------------------------------------------------------------------- */
+shd_status shd_tb_update(shd_ctx* ctx, uint64_t n, const uint32_t* relay, const uint64_t* capacity,
+                         const uint64_t* refill_increment, const uint64_t* refill_interval_ns, uint64_t at_time,
+                         uint32_t* err_relay);
+shd_status shd_inbound_update_buckets(shd_ctx* ctx, uint64_t n, const uint32_t* host, const uint64_t* capacity,
+                                      const uint64_t* refill_increment, const uint64_t* refill_interval_ns,
+                                      uint64_t at_time, uint32_t* err_host);
+shd_status shd_outbound_update_buckets(shd_ctx* ctx, uint64_t n, const uint32_t* host, const uint64_t* capacity,
+                                       const uint64_t* refill_increment, const uint64_t* refill_interval_ns,
+                                       uint64_t at_time, uint32_t* err_host);
+shd_status shd_window_update_bandwidth(shd_ctx* ctx, uint64_t n, const uint32_t* host, const uint64_t* down_bytes_per_s,
+                                       const uint64_t* up_bytes_per_s, uint64_t at_time, uint32_t* err_host);
 
 /* ---------------------------------------------------------------------------------------
  * GML loader (host code, no GPU needed).  Replaces the reference's

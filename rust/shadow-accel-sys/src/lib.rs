@@ -4,7 +4,7 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type shd_status = i32;
-pub const SHD_ABI_VERSION: u32 = 11;
+pub const SHD_ABI_VERSION: u32 = 12;
 pub const SHD_ROUTE_SHORTEST: u32 = 0;
 pub const SHD_ROUTE_DIRECT: u32 = 1;
 pub const SHD_ALGO_AUTO: u32 = 0;
@@ -255,6 +255,10 @@ extern "C" {
     pub fn shd_window_close_staged(ctx: *mut shd_ctx, n_stages: u32, stage_runs: *const u32, run_host: *mut *const u32, run_count: *mut *const u32, stage_offers: *const u64, offers: *mut *const u32, offer_words: u32, time_base: u64, window_end: u64, sim_end: u64, bootstrap_end: u64, sent_pkt: *mut *const u32, sent_status: *mut *const u8, n_batch: *mut u64, n_events: *mut u64, loc_off: *mut *const u32, loc_pkt: *mut *const u32, loc_time: *mut *const u64, n_local: *mut u64, n_stored: *mut u64, outbound_next_task: *mut u64, min_deliver: *mut u64) -> shd_status;
     pub fn shd_window_records_host(ctx: *mut shd_ctx, off: *mut u32, pkt: *mut u32, time: *mut u64, kind: *mut u8, cap: u64, n_out: *mut u64) -> shd_status;
     pub fn shd_window_sent_host(ctx: *mut shd_ctx, sent_pkt: *mut u32, sent_status: *mut u8, cap_batch: u64, loc_off: *mut u32, loc_pkt: *mut u32, loc_time: *mut u64, cap_local: u64, n_batch: *mut u64, n_local: *mut u64) -> shd_status;
+    pub fn shd_tb_update(ctx: *mut shd_ctx, n: u64, relay: *const u32, capacity: *const u64, refill_increment: *const u64, refill_interval_ns: *const u64, at_time: u64, err_relay: *mut u32) -> shd_status;
+    pub fn shd_inbound_update_buckets(ctx: *mut shd_ctx, n: u64, host: *const u32, capacity: *const u64, refill_increment: *const u64, refill_interval_ns: *const u64, at_time: u64, err_host: *mut u32) -> shd_status;
+    pub fn shd_outbound_update_buckets(ctx: *mut shd_ctx, n: u64, host: *const u32, capacity: *const u64, refill_increment: *const u64, refill_interval_ns: *const u64, at_time: u64, err_host: *mut u32) -> shd_status;
+    pub fn shd_window_update_bandwidth(ctx: *mut shd_ctx, n: u64, host: *const u32, down_bytes_per_s: *const u64, up_bytes_per_s: *const u64, at_time: u64, err_host: *mut u32) -> shd_status;
     pub fn shd_gml_parse(text: *const c_char, len: usize, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_load(path: *const c_char, xz: i32, out: *mut *mut shd_gml, msg: *mut c_char, msg_len: usize) -> shd_status;
     pub fn shd_gml_graph(g: *const shd_gml, view: *mut shd_graph) -> shd_status;

@@ -48,6 +48,7 @@ EXPORTED = [
     "shd_outbound_advance_sockets", "shd_window_close_sockets",
     "shd_offers_group", "shd_window_close_staged", "shd_window_records_host", "shd_window_sent_host",
     "shd_routing_update_edges", "shd_relay_retable",
+    "shd_tb_update", "shd_inbound_update_buckets", "shd_outbound_update_buckets", "shd_window_update_bandwidth",
 ]
 COMM_ID_BYTES = 128
 
@@ -259,6 +260,10 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "shd_window_sent_host": (I32, [P, P, P, U64, P, P, P, U64, P, P]),
         "shd_routing_update_edges": (I32, [P, U64, P, P, P, P]),
         "shd_relay_retable": (I32, [P, U32, P, P]),
+        "shd_tb_update": (I32, [P, U64, P, P, P, P, U64, P]),
+        "shd_inbound_update_buckets": (I32, [P, U64, P, P, P, P, U64, P]),
+        "shd_outbound_update_buckets": (I32, [P, U64, P, P, P, P, U64, P]),
+        "shd_window_update_bandwidth": (I32, [P, U64, P, P, P, U64, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -18,7 +18,7 @@ SRC = [os.path.join(HERE, "csrc", f) for f in ("routing_sssp_lds.hip", "relay_st
                                                 "api.cpp", "gml.cpp",
                                                 "codel.hip", "tbucket.hip", "comm.cpp", "equeue_pass.hip", "equeue.hip",
                                                 "hosts.cpp", "rounds.hip", "flush.hip", "inbound.hip",
-                                                "outbound.hip", "offers.hip", "stage_group.hip", "ledger.hip", "scan.hip",
+                                                "outbound.hip", "rate_update.hip", "offers.hip", "stage_group.hip", "ledger.hip", "scan.hip",
                                                 "window.cpp")]
 OUT = os.path.join(HERE, "libshd_accel.so")
 OBJ = os.path.join(HERE, "build", "obj")

@@ -129,4 +129,15 @@ struct CodelLane {
     }
 };
 
+// Every packet of a host's queue, read-only: f(size) over ring[head ... head + count), wrapping.
+template <class F>
+__device__ __forceinline__ void codel_visit(const CodelHost& s, const uint4* ring, uint32_t cap, F&& f) {
+    const uint32_t n = s.count < cap ? s.count : cap;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t j = s.head + i;
+        if (j >= cap) j -= cap;
+        f(ring[j].y);
+    }
+}
+
 }  // namespace shd

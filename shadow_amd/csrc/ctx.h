@@ -8,6 +8,7 @@
 #include "edge_update.h"
 #include "knobs.h"
 #include "ledger_book.h"
+#include "rate_update.h"
 
 namespace shd {
 
@@ -169,6 +170,18 @@ struct OutboundState {
     uint64_t prev_end = 0;         // the last advance's window_end
     bool advanced = false;         // an advance has run since the setup (b_* hold its batch)
     bool ready = false;
+};
+
+// The bucket re-rate (rate_update.hip), per target -- the replay engine's relays, the inbound
+// stage, the outbound stage: the call's records on the device, its two result words (status bits,
+// lowest failing host) and the host's last-entry-wins stamps.
+enum RateTarget : int { kRateTb = 0, kRateInbound = 1, kRateOutbound = 2, kRateTargets = 3 };
+struct RateState {
+    DevBuf rec[kRateTargets];
+    DevBuf words;                            // [kRateTargets][2] u64: status bits, lowest failing host
+    RateStamps stamps[kRateTargets];
+    std::vector<RateRec> host_rec[kRateTargets];   // the records as uploaded (they outlive the copy)
+    uint32_t n_rec[kRateTargets] = {0, 0, 0};   // records of the running call (between its check and its apply)
 };
 
 // The grouping of staged runs by host (stage_group.hip), one per staged entry point: the runs as
@@ -347,8 +360,8 @@ namespace shd {
 // h_pin words: [0, 3) routing flags, [8, 16) relay reductions, [16, 18) the edge update's min / max arc latency,
 // [32, 36) flush checks, [36, 38) offer-group checks,
 // [48, 48 + 4 + runs + 1) event-queue counts, [72, 76) inbound-stage words; [80] is the polled marker;
-// [81, 86) outbound-stage words
-constexpr int kPinWords = 88;
+// [81, 86) outbound-stage words, [88, 94) the bucket re-rate's result words
+constexpr int kPinWords = 96;
 constexpr int kPinMarker = 80;
 // Wait until everything enqueued on stream s has finished (see api.cpp)
 shd_status wait_stream(shd_ctx* ctx, hipStream_t s);
@@ -372,6 +385,18 @@ shd_status relay_round_sharded_local(shd_ctx* ctx, const shd_batch* b, const shd
 // One small collective under a communicator of > 1 ranks (ledger.hip): every rank passes its own
 // status and all return the lowest failing rank's (SHD_OK: none failed); one host synchronisation
 shd_status comm_agree(shd_ctx* ctx, shd_status local);
+// The bucket re-rate in its parts (rate_update.hip).  rate_stage_check: the host-side rules, the records'
+// upload and the check launch; rate_stage_apply: the apply launch, which does nothing where the target's
+// check failed on the device; rate_stage_result: the one read-back of the targets in `mask` (bit per
+// RateTarget) -- SHD_ERR_INVALID and the lowest failing host of the first target that failed.
+// shd_*_update_buckets is check, apply, result; shd_window_update_bandwidth checks both stages
+// and reads the result before it applies either.
+shd_status rate_stage_check(shd_ctx* ctx, RateTarget t, uint64_t n, const uint32_t* host, const uint64_t* capacity,
+                      const uint64_t* increment, const uint64_t* interval, uint64_t at);
+shd_status rate_stage_apply(shd_ctx* ctx, RateTarget t, uint64_t at);
+shd_status rate_stage_result(shd_ctx* ctx, uint32_t mask, uint32_t* err_host);
+shd_status rate_update(shd_ctx* ctx, RateTarget t, uint64_t n, const uint32_t* host, const uint64_t* capacity,
+                       const uint64_t* increment, const uint64_t* interval, uint64_t at, uint32_t* err_host);
 // free the host mirror of the resident table (it follows the table)
 void drop_mirror(shd_ctx* ctx);
 }  // namespace shd
@@ -432,4 +457,5 @@ struct shd_ctx {
     shd::OffersState offers;
     shd::LedgerState ledger;
     shd::WindowState win;
+    shd::RateState rate;
 };

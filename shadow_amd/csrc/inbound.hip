@@ -41,12 +41,13 @@
 
 #include "codel_lane.h"
 #include "ctx.h"
+#include "inbound_relay.h"
 #include "scan.h"
 #include "tbucket_ops.h"
 
 namespace shd {
 
-constexpr uint64_t kInIdle = ~0ull;    // no outstanding forward task
+// (kInIdle and the relay words InRelay: inbound_relay.h)
 constexpr uint32_t kInBatch = 8;       // events per lane loaded ahead of the state machine
 constexpr int kInPinWord = 72;         // ctx->h_pin words [72, 76)
 static_assert(kInPinWord + 4 <= kPinMarker, "inbound words below the polled marker");
@@ -58,11 +59,6 @@ constexpr uint32_t kInRingFull = 8u;
 constexpr uint32_t kInPanic = 16u;     // where the reference panics (token_bucket.rs unwraps)
 constexpr uint32_t kInSpin = 32u;      // the task budget ran out (unreachable under the input contract)
 constexpr uint32_t kInRegion = 64u;    // a record past the host's region (unreachable: one record per packet)
-
-struct InRelay {   // 24 bytes per host
-    uint64_t task;   // time of the outstanding forward task (RelayState::Pending), kInIdle: Idle
-    uint32_t has_cached, cached_pkt, cached_size, pad;   // RelayInternal::next_packet
-};
 
 struct InRecords {   // CodelLane's sink: kind 1 FORWARDED, 2 DROPPED, at the running task's time
     uint32_t* pkt;
@@ -433,6 +429,14 @@ shd_status shd_inbound_get_state(shd_ctx* ctx, uint32_t host, uint64_t* task_tim
         bucket->pending_until = r.task == kInIdle ? 0 : r.task;   // the relay's task, as shd_tb_state names it
     }
     return SHD_OK;
+}
+
+// the hosts' bw_down buckets re-rated at `at_time` (rate_update.hip): queues, CoDel state, the
+// cached packet and the outstanding task stay
+shd_status shd_inbound_update_buckets(shd_ctx* ctx, uint64_t n, const uint32_t* host, const uint64_t* capacity,
+                                      const uint64_t* refill_increment, const uint64_t* refill_interval_ns,
+                                      uint64_t at_time, uint32_t* err_host) {
+    return rate_update(ctx, kRateInbound, n, host, capacity, refill_increment, refill_interval_ns, at_time, err_host);
 }
 
 }  // extern "C"

@@ -201,4 +201,27 @@ SHD_HOST_DEVICE inline uint32_t rr_counts(const RrQueue& q, const RrSlot* pool, 
     return n;
 }
 
+// Every queued packet, read-only: f(size, dst) for the head socket's first packet (the words), its
+// further packets, then each socket of the ring with its chain.  Free slots lie on no chain and
+// are not visited.  (At most `cap` slots are followed in all: a state the functions above left
+// never needs more.)
+template <class F>
+SHD_HOST_DEVICE inline void rr_visit(const RrQueue& q, const RrSlot* pool, uint32_t cap, const RrSock* ring,
+                                     uint32_t max_sockets, F&& f) {
+    if (q.count == 0) return;
+    f(q.size, q.dst);
+    uint32_t steps = 0;
+    for (uint32_t s = q.first; s != kRrNil && s < cap && steps < cap; ++steps) {
+        f(pool[s].size, pool[s].dst);
+        s = pool[s].next;
+    }
+    for (uint32_t i = 0; i < q.ring_count && i < max_sockets; ++i) {
+        const RrSock& e = ring[rr_wrap(q.ring_head + i, max_sockets)];
+        for (uint32_t s = e.first; s != kRrNil && s < cap && steps < cap; ++steps) {
+            f(pool[s].size, pool[s].dst);
+            s = pool[s].next;
+        }
+    }
+}
+
 }  // namespace shd

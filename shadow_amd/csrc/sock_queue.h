@@ -288,4 +288,30 @@ SHD_HOST_DEVICE inline uint32_t sq_counts(const SqQueue& q, const SqSlot* pool, 
     return n;
 }
 
+// Every queued packet, read-only: f(size, dst) for the one packet in the words (n_socks == 0), else
+// for each queued socket's control list and data list.  Free slots lie on no list and are not
+// visited.  (At most `cap` slots are followed in all: a state the functions above left never needs
+// more.)
+template <class F>
+SHD_HOST_DEVICE inline void sq_visit(const SqQueue& q, const SqSlot* pool, uint32_t cap, const SqSock* socks,
+                                     uint32_t max_sockets, bool fifo, F&& f) {
+    if (q.count == 0) return;
+    if (q.n_socks == 0) {
+        f(q.size, q.dst);
+        return;
+    }
+    uint32_t steps = 0;
+    for (uint32_t i = 0; i < q.n_socks && i < max_sockets; ++i) {
+        const SqSock& e = socks[sq_at(q, i, max_sockets, fifo)];
+        for (uint32_t s = e.cfirst; s != kSqNil && s < cap && steps < cap; ++steps) {
+            f(pool[s].size, pool[s].dst);
+            s = pool[s].next;
+        }
+        for (uint32_t s = e.dfirst; s != kSqNil && s < cap && steps < cap; ++steps) {
+            f(pool[s].size, pool[s].dst);
+            s = pool[s].next;
+        }
+    }
+}
+
 }  // namespace shd

@@ -140,4 +140,11 @@ shd_status shd_tb_get_state(shd_ctx* ctx, uint32_t relay, shd_tb_state* out) {
     return SHD_OK;
 }
 
+// the relays' buckets re-rated at `at_time` (rate_update.hip); a Pending relay stays Pending
+shd_status shd_tb_update(shd_ctx* ctx, uint64_t n, const uint32_t* relay, const uint64_t* capacity,
+                         const uint64_t* refill_increment, const uint64_t* refill_interval_ns, uint64_t at_time,
+                         uint32_t* err_relay) {
+    return rate_update(ctx, kRateTb, n, relay, capacity, refill_increment, refill_interval_ns, at_time, err_relay);
+}
+
 }  // extern "C"

@@ -80,6 +80,27 @@ __device__ __forceinline__ bool tb_conforming_remove(TbRelay& s, uint64_t now, u
     return false;
 }
 
+// A re-rate of the relay's bucket at `at` to (capacity C, increment I, interval N), all three 0: no
+// bucket (rate_update.h states the rules).  The old rate holds up to `at`: lazy_refill(at) under
+// the old parameters -- tb_conforming_remove of nothing, with its `bad` conditions -- then
+// new_inner(C, I, N, at) with the balance min(refilled balance, C); a relay without a bucket gets
+// a full one, as every new bucket.  The relay's pending deadline is not touched.
+__device__ __forceinline__ void tb_rerate(TbRelay& s, uint64_t at, uint64_t C, uint64_t I, uint64_t N, bool& bad) {
+    uint64_t balance = C;
+    if (s.capacity) {
+        uint64_t v;
+        (void)tb_conforming_remove(s, at, 0, v, bad);
+        balance = v < C ? v : C;
+    } else if (C == 0) {
+        return;   // no bucket before or after: nothing changes
+    }
+    s.capacity = C;
+    s.balance = balance;
+    s.increment = I;
+    s.interval = N;
+    s.last_refill = at;
+}
+
 // Host rows of a setup call: all three parameters 0 = no bucket; some but not all 0 is
 // SHD_ERR_INVALID (TokenBucket::new -> None, which the reference unwraps).  Buckets start full.
 inline shd_status tb_rows(uint32_t n, const uint64_t* capacity, const uint64_t* refill_increment,

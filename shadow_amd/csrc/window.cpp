@@ -11,6 +11,8 @@
 // into host buffers with one wait each.
 // The stages are the ones the separate calls drive (equeue.hip, ledger.hip, inbound.hip,
 // outbound.hip, relay*.hip); this file only chains them and keeps what lies between two calls.
+#include <vector>
+
 #include "ctx.h"
 #include "offer_stage.h"
 
@@ -384,6 +386,44 @@ shd_status shd_window_close(shd_ctx* ctx, const uint32_t* d_off, const uint64_t*
     return shd_window_close_sockets(ctx, d_off, d_time, d_prio, nullptr, d_size, d_payload, d_dst, d_pkt, n_offers,
                                     window_end, sim_end, bootstrap_end, sent_pkt, sent_status, n_batch, n_events, loc_off,
                                     loc_pkt, loc_time, n_local, n_stored, outbound_next_task, min_deliver);
+}
+
+// Both stages' buckets from new link rates, between a close and the next open.  create_token_bucket
+// (relay/mod.rs:291-302) per direction; UINT64_MAX leaves a direction as it is.  Both stages are
+// checked before either changes: a refusal by one leaves both untouched.
+shd_status shd_window_update_bandwidth(shd_ctx* ctx, uint64_t n, const uint32_t* host, const uint64_t* down_bytes_per_s,
+                                       const uint64_t* up_bytes_per_s, uint64_t at_time, uint32_t* err_host) {
+    if (!ctx) return SHD_ERR_INVALID;
+    if (!window_ready(ctx) || ctx->win.opened) return SHD_ERR_STATE;
+    if (n && (!host || !down_bytes_per_s || !up_bytes_per_s)) return SHD_ERR_INVALID;
+    if (n == 0) return SHD_OK;
+    if (window_own_hosts(ctx) == 0) return SHD_ERR_INVALID;   // (a rank without hosts has no stage: any index is past it)
+    std::vector<uint32_t> hs[2];
+    std::vector<uint64_t> cap[2], inc[2], itv[2];
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t bps[2] = {down_bytes_per_s[i], up_bytes_per_s[i]};
+        for (int d = 0; d < 2; ++d) {
+            if (bps[d] == ~0ull) continue;
+            uint64_t c, k, t;
+            rate_from_bandwidth(bps[d], c, k, t);
+            hs[d].push_back(host[i]);
+            cap[d].push_back(c);
+            inc[d].push_back(k);
+            itv[d].push_back(t);
+        }
+    }
+    // (an index past the stage in a direction that UINT64_MAX skips is still refused)
+    for (uint64_t i = 0; i < n; ++i)
+        if (host[i] >= ctx->inb.n_hosts) return SHD_ERR_INVALID;
+    const RateTarget tg[2] = {kRateInbound, kRateOutbound};
+    shd_status st = SHD_OK;
+    for (int d = 0; d < 2 && st == SHD_OK; ++d)
+        st = rate_stage_check(ctx, tg[d], hs[d].size(), hs[d].data(), cap[d].data(), inc[d].data(), itv[d].data(), at_time);
+    if (st == SHD_OK) st = rate_stage_result(ctx, 1u << kRateInbound | 1u << kRateOutbound, err_host);
+    for (int d = 0; d < 2 && st == SHD_OK; ++d) st = rate_stage_apply(ctx, tg[d], at_time);
+    if (st == SHD_OK) st = wait_stream(ctx, ctx->stream);
+    ctx->rate.n_rec[kRateInbound] = ctx->rate.n_rec[kRateOutbound] = 0;
+    return st;
 }
 
 }  // extern "C"

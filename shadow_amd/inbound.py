@@ -22,7 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .tbucket import SIM_START, create_token_bucket
+from .tbucket import SIM_START, bandwidth_rows, create_token_bucket, update_buckets
 
 FORWARDED, DROPPED = 1, 2
 IDLE = 2**64 - 1
@@ -115,6 +115,19 @@ class InboundStage:
                 N.check(self.eng.lib.shd_copy_to_host(self.eng.ctx, N.ptr(dst), C.c_void_p(src), dst.nbytes),
                         "shd_copy_to_host")
         return Records(off, pkt, time, kind, out.n_stored, out.next_task_time)
+
+    def update_buckets(self, hosts, capacity, refill_increment, refill_interval, at_time: int):
+        """``shd_inbound_update_buckets``: the named hosts' ``bw_down`` buckets re-rated at
+        ``at_time`` (>= the last ``window_end``; all three parameters 0: no bucket).  Queues, CoDel
+        state, the cached packet and the outstanding task stay as they are.  A refusal (ShdError,
+        ``.host`` the lowest failing host) changes nothing."""
+        update_buckets(self.eng, "shd_inbound_update_buckets", hosts, capacity, refill_increment, refill_interval,
+                       at_time)
+
+    def update_bandwidth(self, hosts, bytes_per_second, at_time: int):
+        """``update_buckets`` with ``create_token_bucket`` per entry, as ``from_bandwidth`` (None:
+        no bucket)."""
+        self.update_buckets(hosts, *bandwidth_rows(bytes_per_second), at_time)
 
     def state(self, host: int) -> dict:
         """One host: ``task_time`` (None: Idle), ``cached`` ((pkt, size) or None), the queue as

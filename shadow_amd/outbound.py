@@ -35,7 +35,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as N
-from .tbucket import SIM_START, create_token_bucket
+from .tbucket import SIM_START, bandwidth_rows, create_token_bucket, update_buckets
 
 IDLE = 2**64 - 1
 NO_PKT = 2**32 - 1
@@ -349,6 +349,20 @@ class OutboundStage:
                 N.check(self.eng.lib.shd_copy_to_host(self.eng.ctx, N.ptr(dst), C.c_void_p(src), dst.nbytes),
                         "shd_copy_to_host")
         return Sent(src_off, t, d, p, sp, loc_off, lp, lt, out.n_stored, out.next_task_time)
+
+    def update_buckets(self, hosts, capacity, refill_increment, refill_interval, at_time: int):
+        """``shd_outbound_update_buckets``: the named hosts' ``bw_up`` buckets re-rated at
+        ``at_time`` (>= the last ``window_end``; all three parameters 0: no bucket).  ``hosts`` are
+        the stage's own indices (global id ``first_host + h``).  Queues, sockets, the cached packet
+        and the outstanding task stay as they are.  A refusal (ShdError, ``.host`` the lowest
+        failing host) changes nothing."""
+        update_buckets(self.eng, "shd_outbound_update_buckets", hosts, capacity, refill_increment, refill_interval,
+                       at_time)
+
+    def update_bandwidth(self, hosts, bytes_per_second, at_time: int):
+        """``update_buckets`` with ``create_token_bucket`` per entry, as ``from_bandwidth`` (None:
+        no bucket)."""
+        self.update_buckets(hosts, *bandwidth_rows(bytes_per_second), at_time)
 
     def sockets(self, host: int) -> list:
         """One host's queued sockets: ``[(handle, queued packets), ...]`` -- in rrQueue order under

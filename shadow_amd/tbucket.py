@@ -30,6 +30,33 @@ def create_token_bucket(bytes_per_second: int) -> tuple[int, int, int]:
     return refill + MTU, refill, MS
 
 
+UNCHANGED = 2**64 - 1   # shd_window_update_bandwidth: leave this direction as it is
+
+
+def bandwidth_rows(bytes_per_second):
+    """``create_token_bucket`` per entry -> (capacity, increment, interval) u64 arrays; an entry of
+    ``None`` (or a negative one) is a host without a bucket, as ``from_bandwidth`` reads it."""
+    rows = [(0, 0, 0) if b is None or int(b) < 0 else create_token_bucket(int(b)) for b in bytes_per_second]
+    return tuple(np.array([r[i] for r in rows], np.uint64) for i in range(3))
+
+
+def update_buckets(engine, fn_name: str, hosts, capacity, refill_increment, refill_interval, at_time: int):
+    """One re-rate call (``shd_tb_update`` / ``shd_inbound_update_buckets`` /
+    ``shd_outbound_update_buckets``): host arrays, one entry per named host; a host named twice
+    takes its last entry.  A refusal raises ShdError whose ``host`` is the lowest failing host the
+    device found (None: refused before any launch)."""
+    h = np.ascontiguousarray(hosts, np.uint32)
+    cap, inc, itv = (np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.uint64), h.shape))
+                     for a in (capacity, refill_increment, refill_interval))
+    err = C.c_uint32(0xFFFFFFFF)
+    st = getattr(engine.lib, fn_name)(engine.ctx, len(h), N.ptr(h), N.ptr(cap), N.ptr(inc), N.ptr(itv), int(at_time),
+                                      C.byref(err))
+    if st != N.SHD_OK:
+        e = N.ShdError(st, fn_name)
+        e.host = None if err.value == 0xFFFFFFFF else err.value
+        raise e
+
+
 class TokenBuckets:
     def __init__(self, engine, capacity, refill_increment, refill_interval, last_refill=SIM_START):
         self.eng = engine
@@ -60,6 +87,16 @@ class TokenBuckets:
         torch.cuda.synchronize()
         N.check(st, "shd_tb_run_device")
         return status.cpu().numpy()[:n].copy(), value.cpu().numpy().view(np.uint64)[:n].copy()
+
+    def update_buckets(self, relays, capacity, refill_increment, refill_interval, at_time: int):
+        """``shd_tb_update``: the named relays' buckets re-rated at ``at_time`` (all three
+        parameters 0: no bucket).  The old rate holds up to ``at_time``; the balance carries over,
+        clamped to the new capacity; a Pending relay stays Pending."""
+        update_buckets(self.eng, "shd_tb_update", relays, capacity, refill_increment, refill_interval, at_time)
+
+    def update_bandwidth(self, relays, bytes_per_second, at_time: int):
+        """``update_buckets`` with ``create_token_bucket`` per entry (None: no bucket)."""
+        self.update_buckets(relays, *bandwidth_rows(bytes_per_second), at_time)
 
     def state(self, relay: int) -> dict:
         s = N.TbState()

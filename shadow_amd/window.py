@@ -117,6 +117,25 @@ class Window:
         return Closed(sp.value, ss.value, lo.value, lp.value, lt.value, n_batch.value, n_ev.value, n_local.value,
                       n_stored.value, nxt.value, md.value)
 
+    def update_bandwidth(self, hosts, down_bytes_per_second, up_bytes_per_second, at_time: int):
+        """``shd_window_update_bandwidth``: between a close and the next open, both stages'
+        buckets of the named hosts (the engine's own indices) from new link rates in bytes per
+        second, ``create_token_bucket`` per direction; an entry of ``None`` leaves that direction
+        as it is.  Both stages are checked before either changes.  A refusal (ShdError, ``.host``
+        the lowest failing host of the stage that refused) changes nothing."""
+        from .tbucket import UNCHANGED
+        h = np.ascontiguousarray(hosts, np.uint32)
+        rate = lambda a: np.array([UNCHANGED if b is None else int(b) for b in a], np.uint64)  # noqa: E731
+        down, up = rate(down_bytes_per_second), rate(up_bytes_per_second)
+        assert len(down) == len(up) == len(h)
+        err = C.c_uint32(0xFFFFFFFF)
+        st = self.eng.lib.shd_window_update_bandwidth(self.eng.ctx, len(h), N.ptr(h), N.ptr(down), N.ptr(up),
+                                                      int(at_time), C.byref(err))
+        if st != N.SHD_OK:
+            e = N.ShdError(st, "shd_window_update_bandwidth")
+            e.host = None if err.value == 0xFFFFFFFF else err.value
+            raise e
+
     def records_host(self, o: Opened) -> Records:
         """``records`` in one engine call (``shd_window_records_host``): every array copied
         asynchronously, one wait.  ``o`` must be the last open."""
