@@ -612,8 +612,15 @@ shd_status shd_codel_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t capacity);
 /* Run a batch.  pop_out[k] = packet id a pop returned (SHD_CODEL_POP for none or for a push);
  * fate[id] = (op index << 2) | 1 (dequeued) or | 2 (dropped) for every packet this batch
  * dequeued or dropped (other entries untouched).  SHD_ERR_INVALID: a queue exceeded its
- * capacity or a packet id >= n_ids (the batch ran with the affected pushes/marks skipped, so the
- * queues are left undefined: every later call returns SHD_ERR_STATE until shd_codel_setup). */
+ * capacity or a packet id >= n_ids (the batch ran with the affected pushes/marks skipped), or the
+ * reference panics: the control law (codel_queue.rs:287-300) of a time before SIMULATION_START
+ * (to_abs_simtime) or with a result past EMUTIME_MAX = 2^64 - 2 (SimulationTime::saturating_add's
+ * unwrap: no saturation there).  The queues are then left undefined: every later call returns
+ * SHD_ERR_STATE until shd_codel_setup.
+ * Times are EmulatedTimes, at most EMUTIME_MAX (2^64 - 1 is EMUTIME_INVALID).  interval_end =
+ * now + INTERVAL saturates at EMUTIME_MAX (EmulatedTime::saturating_add); the standing delay and
+ * the "dropping recently" span are saturating_duration_since: 0 when the earlier time is the
+ * later one and when the difference is above SIMTIME_MAX = 17500059273709551614. */
 shd_status shd_codel_run_device(shd_ctx* ctx, const shd_codel_ops* ops, uint32_t* pop_out,
                                 uint64_t* fate, uint32_t n_ids);
 shd_status shd_codel_get_state(shd_ctx* ctx, uint32_t host, shd_codel_state* out);
@@ -648,15 +655,22 @@ typedef struct shd_tb_state {   /* one relay's bucket, for inspection (the refer
 
 /* (Re)create n_relays buckets (TokenBucket::new_inner, token_bucket.rs:37-60; full at start).
  * All three parameters 0 = no bucket (RateLimit::Unlimited); some but not all 0 is
- * SHD_ERR_INVALID (the reference's new() returns None and its caller unwraps).  Host arrays;
+ * SHD_ERR_INVALID (the reference's new() returns None and its caller unwraps), and so is a bucket
+ * whose refill_interval_ns is above SIMTIME_MAX = 17500059273709551614 (no SimulationTime) or whose
+ * last_refill is above EMUTIME_MAX = 2^64 - 2 (no EmulatedTime), before anything runs.  These rules
+ * hold for the tb_* arrays of shd_inbound_setup and the outbound setups too.  Host arrays;
  * create_token_bucket (relay/mod.rs:291-302) is capacity = max(1, Bps/1000) + 1500,
  * increment = max(1, Bps/1000), interval = 1 ms. */
 shd_status shd_tb_setup(shd_ctx* ctx, uint32_t n_relays, const uint64_t* capacity,
                         const uint64_t* refill_increment, const uint64_t* refill_interval_ns,
                         const uint64_t* last_refill);
 /* Run a batch (device pointers); status[k] / value[k] per attempt.  SHD_ERR_INVALID where the
- * reference panics (a time before the bucket's last refill, a SimulationTime past SIMTIME_MAX);
- * the batch still ran. */
+ * reference panics: a time before the bucket's last refill or more than SIMTIME_MAX after it
+ * (duration_since, token_bucket.rs:128,152), or a conforming duration whose product or sum lies in
+ * (SIMTIME_MAX, 2^64) (SimulationTime::saturating_mul / saturating_add saturate at SIMTIME_MAX only
+ * when the u64 operation overflows; below that they unwrap); the batch still ran.  The token
+ * product and sum saturate at 2^64 - 1; a blocked relay's deadline now + duration saturates at
+ * EMUTIME_MAX (EmulatedTime::saturating_add). */
 shd_status shd_tb_run_device(shd_ctx* ctx, const shd_tb_ops* ops, uint8_t* status, uint64_t* value);
 shd_status shd_tb_get_state(shd_ctx* ctx, uint32_t relay, shd_tb_state* out);
 
@@ -708,7 +722,10 @@ shd_status shd_inbound_setup(shd_ctx* ctx, uint32_t n_hosts, uint32_t capacity,
  * SHD_ERR_INVALID: the input contract is violated, d_off is not a CSR over n_events events, or a
  * queue exceeded its capacity -- every such input is refused by a check in the kernel, the
  * window has partly run, and every later call returns SHD_ERR_STATE until shd_inbound_setup; also
- * where the reference panics (a time before a bucket's last refill).  A NULL array with
+ * where the reference panics (the bucket's cases of shd_tb_run_device, the CoDel control law's of
+ * shd_codel_run_device).  A window_end above EMUTIME_MAX = 2^64 - 2 is no time of the reference's:
+ * a relay blocked for a saturated duration has its task at EMUTIME_MAX, which no window runs.  A
+ * NULL array with
  * n_events > 0 or a window_end below the previous one is SHD_ERR_INVALID before anything runs.
  */
 shd_status shd_inbound_advance(shd_ctx* ctx, const uint32_t* d_off, const uint64_t* d_time,
@@ -856,7 +873,7 @@ shd_status shd_outbound_setup_qdisc(shd_ctx* ctx, uint32_t n_hosts, uint32_t fir
  * weighed against the task), d_off is not a CSR over n_offers offers, a priority equals one still
  * queued on that host (FIFO), or a queue exceeded its capacity or its max_sockets -- every such input is refused by a check
  * in the kernel, the window has partly run, and every later call returns SHD_ERR_STATE until
- * shd_outbound_setup; also where the reference panics (a time before a bucket's last refill).  A
+ * shd_outbound_setup; also where the reference panics (the bucket's cases of shd_tb_run_device).  A
  * NULL array with n_offers > 0 or a window_end below the previous one is SHD_ERR_INVALID before
  * anything runs.
  *
@@ -1178,10 +1195,12 @@ shd_status shd_window_sent_host(shd_ctx* ctx, uint32_t* sent_pkt, uint8_t* sent_
  *   SHD_ERR_STATE    the stage is not ready: before its setup, and after a contract error until
  *                    the next setup (where the advance returns it)
  *   SHD_ERR_INVALID  before any launch: a NULL array with n > 0; an index >= the stage's hosts;
- *                    some-but-not-all-zero parameters; at_time below the stage's previous window_end
+ *                    some-but-not-all-zero parameters; at_time below the stage's previous window_end;
+ *                    an interval above SIMTIME_MAX or an at_time above EMUTIME_MAX: no values of
+ *                    the reference's types
  *   SHD_ERR_INVALID  on the device, for any named host, the lowest such index in *err_host (may be
- *                    NULL; untouched otherwise): at_time before the bucket's last_refill (the
- *                    reference's duration_since would panic); a refill to at_time where the
+ *                    NULL; untouched otherwise): at_time before the bucket's last_refill or more
+ *                    than SIMTIME_MAX after it (the reference's duration_since would panic); a refill to at_time where the
  *                    reference panics (as the advance's); an outstanding forward task earlier than
  *                    at_time (it would run before the new bucket's last_refill); a capacity C > 0
  *                    below the total size of a packet the host stores now, the cached one

@@ -38,6 +38,8 @@ def lib():
                                        C.c_uint32, P, P, C.c_int, P]
         _lib.orc_codel_run.restype = None
         _lib.orc_codel_run.argtypes = [C.c_uint32, P, P, P, P, P, P, C.c_uint32, C.c_int]
+        _lib.orc_codel_run_checked.restype = C.c_int64
+        _lib.orc_codel_run_checked.argtypes = [C.c_uint32, P, P, P, P, P, P, C.c_uint32, P, C.c_int]
         _lib.orc_tb_run.restype = C.c_int64
         _lib.orc_tb_run.argtypes = [C.c_uint32, P, P, P, P, P, P, P, P, P, P, C.c_int]
         _lib.orc_direct_paths.restype = C.c_int
@@ -149,6 +151,19 @@ def codel_run(n_hosts, off, time, size, pkt, n_ids, threads=0):
                         _p(np.ascontiguousarray(size, np.uint32)), _p(np.ascontiguousarray(pkt, np.uint32)),
                         _p(pop), _p(fate), n_ids, threads)
     return pop, fate
+
+
+def codel_run_checked(n_hosts, off, time, size, pkt, n_ids, threads=0):
+    """As codel_run, with the hosts where the reference panics -> (pop_out, fate, panicked u8[n_hosts])."""
+    pop = np.zeros(len(time), np.uint32)
+    fate = np.zeros(n_ids, np.uint64)
+    panicked = np.zeros(max(n_hosts, 1), np.uint8)
+    k = lib().orc_codel_run_checked(n_hosts, _p(np.ascontiguousarray(off, np.uint32)),
+                                    _p(np.ascontiguousarray(time, np.uint64)), _p(np.ascontiguousarray(size, np.uint32)),
+                                    _p(np.ascontiguousarray(pkt, np.uint32)), _p(pop), _p(fate), n_ids, _p(panicked),
+                                    threads)
+    assert int(k) == int(panicked[:n_hosts].sum())
+    return pop, fate, panicked[:n_hosts]
 
 
 def tb_run(capacity, increment, interval, last_refill, off, time, size, flags, threads=0):

@@ -3,7 +3,8 @@
 Restates ``src/main/network/relay/token_bucket.rs:6-157`` (FlyearthR/shadow): ``new_inner``
 (None unless capacity, refill increment and refill interval are all non-zero), ``lazy_refill``
 (whole elapsed refill intervals, tokens ``increment.saturating_mul(n)``, balance clamped to the
-capacity, ``last_refill`` advanced by ``interval * n``), ``conforming_remove`` (the balance after
+capacity, ``last_refill`` advanced by ``interval * n``; both spans are ``duration_since``, which
+panics for ``now`` before ``last_refill`` and for a difference above SIMTIME_MAX), ``conforming_remove`` (the balance after
 the removal, or the duration to the refill boundary after which the removal would conform) and
 ``compute_conforming_duration``; ``create_token_bucket`` (``relay/mod.rs:291-302``: 1 ms refill
 interval, ``max(1, bytes_per_second / 1000)`` tokens per refill, capacity = that + CONFIG_MTU
@@ -30,32 +31,55 @@ EXEMPT = 1   # op flag: local packet or bootstrapping (no tokens taken)
 
 
 class ReferencePanic(Exception):
-    """Where the reference would panic (an unwrap on an out-of-range time)."""
+    """Where the reference would panic (an unwrap on an out-of-range time).  ``kind`` names the
+    operation that unwraps: "span" / "span2" (lazy_refill's first / second duration_since), "product" (SimulationTime::saturating_mul),
+    "sum" (SimulationTime::saturating_add), "abs" (EmulatedTime::to_abs_simtime)."""
+
+    def __init__(self, kind: str, what: str = ""):
+        super().__init__(f"{kind}: {what}" if what else kind)
+        self.kind = kind
 
 
-def _simtime(v: int) -> int:
+def _simtime(v: int, kind: str) -> int:
     """SimulationTime::from_c_simtime(v).unwrap() (simulation_time.rs:36-47)."""
     if v > SIMTIME_MAX:
-        raise ReferencePanic("SimulationTime out of range")
+        raise ReferencePanic(kind, "SimulationTime out of range")
     return v
 
 
 def simtime_sat_mul(t: int, k: int) -> int:
-    """SimulationTime::saturating_mul (simulation_time.rs:145-148)."""
+    """SimulationTime::saturating_mul (simulation_time.rs:145-148): SIMTIME_MAX when the u64
+    product overflows; a product in (SIMTIME_MAX, 2^64) is not saturated -- the unwrap panics."""
     p = t * k
-    return SIMTIME_MAX if p > U64_MAX else _simtime(p)
+    return SIMTIME_MAX if p > U64_MAX else _simtime(p, "product")
 
 
 def simtime_sat_add(a: int, b: int) -> int:
-    """SimulationTime::saturating_add (simulation_time.rs:135-138)."""
+    """SimulationTime::saturating_add (simulation_time.rs:135-138); as saturating_mul."""
     s = a + b
-    return SIMTIME_MAX if s > U64_MAX else _simtime(s)
+    return SIMTIME_MAX if s > U64_MAX else _simtime(s, "sum")
 
 
 def emutime_sat_add(t: int, d: int) -> int:
-    """EmulatedTime::saturating_add (emulated_time.rs:95-108)."""
+    """EmulatedTime::saturating_add (emulated_time.rs:95-108): EMUTIME_MAX = 2^64 - 2 when the
+    u64 sum overflows or is EMUTIME_INVALID."""
     s = t + d
     return EMUTIME_MAX if s > EMUTIME_MAX else s
+
+
+def duration_since(later: int, earlier: int, kind: str = "span") -> int:
+    """EmulatedTime::duration_since (emulated_time.rs:79-87): checked_duration_since(..).unwrap(),
+    None when ``earlier`` is later and when the difference is above SIMTIME_MAX."""
+    if later < earlier:
+        raise ReferencePanic(kind, "duration_since: earlier is later")
+    return _simtime(later - earlier, kind)
+
+
+def saturating_duration_since(later: int, earlier: int) -> int:
+    """EmulatedTime::saturating_duration_since (emulated_time.rs:89-93): ZERO wherever
+    checked_duration_since is None -- ``earlier`` is later, or the difference is above SIMTIME_MAX."""
+    d = later - earlier
+    return 0 if d < 0 or d > SIMTIME_MAX else d
 
 
 def create_token_bucket(bytes_per_second: int) -> tuple[int, int, int]:
@@ -66,9 +90,13 @@ def create_token_bucket(bytes_per_second: int) -> tuple[int, int, int]:
 
 class TokenBucket:
     def __init__(self, capacity: int, refill_increment: int, refill_interval: int, last_refill: int):
-        """new_inner (token_bucket.rs:37-60); ValueError where the reference returns None."""
+        """new_inner (token_bucket.rs:37-60); ValueError where the reference returns None, and
+        for arguments that are no values of its types (a SimulationTime above SIMTIME_MAX, an
+        EmulatedTime above EMUTIME_MAX: from_c_simtime / from_c_emutime give None)."""
         if not (capacity > 0 and refill_increment > 0 and refill_interval > 0):
             raise ValueError("token bucket needs a positive capacity, increment and interval")
+        if refill_interval > SIMTIME_MAX or last_refill > EMUTIME_MAX:
+            raise ValueError("refill interval above SIMTIME_MAX or last_refill above EMUTIME_MAX")
         self.capacity = capacity
         self.balance = capacity
         self.refill_increment = refill_increment
@@ -77,18 +105,14 @@ class TokenBucket:
 
     def lazy_refill(self, now: int) -> int:
         """token_bucket.rs:127-157; returns the span to the next refill."""
-        if now < self.last_refill:
-            raise ReferencePanic("duration_since: now before last_refill")
-        span = now - self.last_refill
+        span = duration_since(now, self.last_refill)
         if span >= self.refill_interval:
             n = span // self.refill_interval
             tokens = min(self.refill_increment * n, U64_MAX)         # u64::saturating_mul
             self.balance = min(min(self.balance + tokens, U64_MAX), self.capacity)
             inc = simtime_sat_mul(self.refill_interval, n)
             self.last_refill = emutime_sat_add(self.last_refill, inc)
-            if now < self.last_refill:
-                raise ReferencePanic("duration_since: now before last_refill")
-            span = now - self.last_refill
+            span = duration_since(now, self.last_refill, "span2")
         return self.refill_interval - span
 
     def compute_conforming_duration(self, decrement: int, next_refill_span: int) -> int:

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void codel_run(uint32_t n_hosts, const uint32_
         }
     }
     st[h] = L.s;
-    flags_arr[h] = L.flags;
+    flags_arr[h] = L.flags & ~kCodelPanic;
+    if (L.flags & kCodelPanic) atomicOr(status, 4u);   // where the reference panics (the control law)
 }
 
 }  // namespace shd
@@ -122,8 +123,8 @@ shd_status shd_codel_run_device(shd_ctx* ctx, const shd_codel_ops* ops, uint32_t
     SHD_HIP(hipStreamSynchronize(s));
     const uint32_t st = (uint32_t)ctx->h_pin[24];
     if (st) {
-        // the batch ran with the offending pushes / marks skipped: the queues now hold a state
-        // the reference never reaches (and a ring slot freed by a pop may have been reused), so
+        // the batch ran with the offending pushes / marks skipped, or past a point where the
+        // reference panics: the queues now hold a state the reference never reaches (and a ring slot freed by a pop may have been reused), so
         // they cannot be rolled back -- shd_codel_setup must run again before the next batch
         C.ready = false;
         return SHD_ERR_INVALID;

@@ -56,7 +56,7 @@ constexpr uint32_t kInBadOff = 1u;     // offsets not monotone / not covering n_
 constexpr uint32_t kInBadTime = 2u;    // an event before its predecessor (or the last window), or >= window_end
 constexpr uint32_t kInBadPkt = 4u;     // a size above the bucket's capacity, or packet id UINT32_MAX
 constexpr uint32_t kInRingFull = 8u;
-constexpr uint32_t kInPanic = 16u;     // where the reference panics (token_bucket.rs unwraps)
+constexpr uint32_t kInPanic = 16u;     // where the reference panics (token_bucket.rs / codel_queue.rs unwraps)
 constexpr uint32_t kInSpin = 32u;      // the task budget ran out (unreachable under the input contract)
 constexpr uint32_t kInRegion = 64u;    // a record past the host's region (unreachable: one record per packet)
 
@@ -222,11 +222,11 @@ __global__ __launch_bounds__(256) void inb_run(uint32_t n_hosts, const uint32_t*
                 break;
             }
         }
-        if (bad) err |= kInPanic;
+        if (bad || (L.flags & kCodelPanic)) err |= kInPanic;
         if (L.sink.over) err |= kInRegion;
         if (err) atomicOr(status, err);
         st[h] = L.s;
-        flags_arr[h] = L.flags;
+        flags_arr[h] = L.flags & ~kCodelPanic;
         tb[h] = B;
         rl[h] = R;
         n_out = L.sink.w - base;

@@ -8,12 +8,15 @@
 // lazy_refill(at) under the old parameters (token_bucket.rs:127-157), then
 // TokenBucket::new_inner(C, I, N, at) (:37-60) whose balance is min(refilled balance, C) instead
 // of C.  All three 0: the host becomes unlimited; some but not all 0 is refused, as at setup
-// (tb_rows, tbucket_ops.h).  The device side (tb_rerate, tbucket_ops.h) does the arithmetic.
+// (tb_rows, tbucket_ops.h), and so is an interval above SIMTIME_MAX (no SimulationTime) or an `at`
+// above EMUTIME_MAX (no EmulatedTime: `at` is the refill's `now` and the new last_refill).  The device side (tb_rerate, tbucket_ops.h) does the arithmetic.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <vector>
+
+#include "time_limits.h"
 
 namespace shd {
 
@@ -40,12 +43,13 @@ inline bool rate_updates_valid(uint64_t n, uint32_t n_hosts, const uint32_t* hos
                                const uint64_t* increment, const uint64_t* interval, uint64_t at, uint64_t prev_end) {
     if (n == 0) return true;   // an empty call does nothing, whatever its time
     if (!host || !capacity || !increment || !interval) return false;
-    if (at < prev_end) return false;
+    if (at < prev_end || at > kEmutimeMax) return false;
     for (uint64_t i = 0; i < n; ++i) {
         if (host[i] >= n_hosts) return false;
         const bool any = capacity[i] || increment[i] || interval[i];
         const bool all = capacity[i] && increment[i] && interval[i];
         if (any && !all) return false;
+        if (interval[i] > kSimtimeMax) return false;   // new_inner(C, I, N, at): N is a SimulationTime
     }
     return true;
 }

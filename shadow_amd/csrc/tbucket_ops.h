@@ -9,20 +9,20 @@
 //   :94-120  compute_conforming_duration: ceil(missing / increment) refills; 0 -> ZERO,
 //            1 -> the span to the next refill, n -> span + interval * (n - 1), saturating
 //   :127-157 lazy_refill: n = elapsed / interval whole refills, balance + increment * n
-//            (u64 saturating) clamped to the capacity, last_refill += interval * n
+//            (u64 saturating) clamped to the capacity, last_refill += interval * n; both spans
+//            are duration_since (emulated_time.rs:79-87): now before last_refill panics, and so
+//            does a difference above SIMTIME_MAX
 // Times: EmulatedTime ns (u64); SimulationTime saturates at SIMTIME_MAX, EmulatedTime at
-// EMUTIME_MAX.  A product or sum beyond SIMTIME_MAX that does not overflow u64 is where the
+// EMUTIME_MAX.  A product, sum or span beyond SIMTIME_MAX that does not overflow u64 is where the
 // reference panics (from_c_simtime(..).unwrap()); `bad` records it.
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "common.h"
+#include "time_limits.h"
 
 namespace shd {
-
-constexpr uint64_t kSimtimeMax = 17500059273709551614ull;   // simulation_time.rs:377
-constexpr uint64_t kEmutimeMax = ~0ull - 1ull;               // emulated_time.rs:27
 
 struct TbRelay {   // 48 bytes per relay; capacity 0 = no bucket (unlimited)
     uint64_t capacity, balance, increment, interval, last_refill, pending;
@@ -53,17 +53,22 @@ __device__ __forceinline__ uint64_t emutime_sat_add(uint64_t t, uint64_t d) {
 __device__ __forceinline__ bool tb_conforming_remove(TbRelay& s, uint64_t now, uint64_t dec, uint64_t& v,
                                                      bool& bad) {
     // lazy_refill (token_bucket.rs:127-157)
-    const bool before = now < s.last_refill;   // duration_since(..).unwrap() panics
+    // duration_since(..).unwrap() panics: now is earlier, or the span is no SimulationTime (one
+    // compare for both: an earlier now counts as the largest span)
+    uint64_t span = now < s.last_refill ? ~0ull : now - s.last_refill;
+    const bool before = span > kSimtimeMax;
     bad |= before;
-    uint64_t span = before ? 0ull : now - s.last_refill;
+    span = before ? 0ull : span;
     if (span >= s.interval) {
         const uint64_t n = span / s.interval;
         const uint64_t tok = __umul64hi(s.increment, n) ? ~0ull : s.increment * n;
         const uint64_t sum = s.balance + tok < s.balance ? ~0ull : s.balance + tok;
         s.balance = sum < s.capacity ? sum : s.capacity;
         s.last_refill = emutime_sat_add(s.last_refill, simtime_sat_mul(s.interval, n, bad));
-        bad |= now < s.last_refill;
-        span = now < s.last_refill ? 0ull : now - s.last_refill;
+        span = now < s.last_refill ? ~0ull : now - s.last_refill;
+        const bool before2 = span > kSimtimeMax;
+        bad |= before2;
+        span = before2 ? 0ull : span;
     }
     const uint64_t next_span = s.interval - span;
     if (s.balance >= dec) {
@@ -102,7 +107,9 @@ __device__ __forceinline__ void tb_rerate(TbRelay& s, uint64_t at, uint64_t C, u
 }
 
 // Host rows of a setup call: all three parameters 0 = no bucket; some but not all 0 is
-// SHD_ERR_INVALID (TokenBucket::new -> None, which the reference unwraps).  Buckets start full.
+// SHD_ERR_INVALID (TokenBucket::new -> None, which the reference unwraps), and so is a bucket
+// whose interval is no SimulationTime (above SIMTIME_MAX) or whose last_refill is no EmulatedTime
+// (above EMUTIME_MAX): from_c_simtime / from_c_emutime give None.  Buckets start full.
 inline shd_status tb_rows(uint32_t n, const uint64_t* capacity, const uint64_t* refill_increment,
                           const uint64_t* refill_interval_ns, const uint64_t* last_refill,
                           std::vector<TbRelay>& h) {
@@ -112,6 +119,7 @@ inline shd_status tb_rows(uint32_t n, const uint64_t* capacity, const uint64_t* 
         const bool any = capacity[r] || refill_increment[r] || refill_interval_ns[r];
         const bool all = capacity[r] && refill_increment[r] && refill_interval_ns[r];
         if (any && !all) return SHD_ERR_INVALID;
+        if (all && (refill_interval_ns[r] > kSimtimeMax || last_refill[r] > kEmutimeMax)) return SHD_ERR_INVALID;
         h[r] = TbRelay{capacity[r], capacity[r], refill_increment[r], refill_interval_ns[r], last_refill[r], 0};
     }
     return SHD_OK;

@@ -150,6 +150,24 @@ def test_refusals(exe):
     assert a == [(3, 1, 1, 1)] and b is None
 
 
+def test_refusals_of_values_outside_the_time_types(exe):
+    """An interval above SIMTIME_MAX is no SimulationTime, an `at` above EMUTIME_MAX no EmulatedTime
+    (the refill's `now`, the new bucket's last_refill): refused; the types' largest values pass."""
+    smax, emax = 17500059273709551614, 2**64 - 2
+    one = lambda text: parse(run(exe, "stage 10 0\n" + text))[0]  # noqa: E731
+    assert one(update([1], [5], [5], [smax], at=emax)) == [(1, 5, 5, smax)]
+    assert one(update([1], [5], [5], [smax + 1], at=1000)) is None
+    assert one(update([1, 2], [5, 5], [5, 5], [5, 2**64 - 1], at=1000)) is None
+    assert one(update([2, 2], [5, 5], [5, 5], [smax + 1, 5], at=1000)) is None   # also in a replaced entry
+    assert one(update([1], [5], [5], [5], at=emax + 1)) is None
+    assert one(update([1], [0], [0], [0], at=emax + 1)) is None
+    assert one(update([], [], [], [], at=emax + 1)) == []                        # (an empty call does nothing)
+    # the model refuses the same values
+    for itv, at in ((smax + 1, 1000), (5, emax + 1)):
+        with pytest.raises(ValueError):
+            rerate(None, at, 5, 5, itv)
+
+
 def test_bandwidth_rows_are_create_token_bucket(exe):
     rates = [0, 1, 999, 1000, 1001, 125_000, 10**9, 2**40 + 12345]
     lines = run(exe, "".join(f"bandwidth {b}\n" for b in rates))
